@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: batched centroidal-MPC solves per second (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the one JSON line (headline `value`, `ms_per_step`,
+outcome, iteration / KKT quantiles, roofline of the timed launches).  --full adds the legs that take runs of
+their own (pipelined, warm_start, batch_sweep, seeds, wbc_qp, cpu_baseline below).  --dump-outputs DIR writes
+what the last timed step returned as DIR/<name>.npy (see dump_outputs).
 
 N > 1 either arrives from `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK /
 LOCAL_RANK / WORLD_SIZE in the environment) or, when the command is started bare (`python bench.py --gpus 8`),
@@ -20,17 +25,18 @@ are counted as solves.  The same JSON line also carries
   outcome       fractions of the batch per status: converged / acceptable (status 3: KKT <= 1e-4, tighter
                 than the reference's own IPOPT tolerance 1e-3) / locally infeasible / iteration cap, and the
                 rates `usable_solves_per_s` (status 0 or 3) and `all_instances_per_s`
+  roofline      HBM classification of SURVEY.md 8d: algorithmic bytes B_io per solve x solves per launch /
+                kernel time (HIP events on the launch stream, non-overlapped launch) vs 8 TB/s
+  iterations / kkt quantiles of the timed batch (SURVEY 8d "Metric" row), per-rank step time and gather time at N > 1
+and, with --full (world size 1),
   pipelined     the same steps alternating over two solver handles on two HIP streams (independent batches
                 only: the drain of one launch -- its longest instance -- overlaps the next launch)
   warm_start    every instance re-solved from its own solution and solver state (cmpc_solve_batch_state: the
                 closed-loop entry point; the closed loop proper is tools/walk_demo.py)
   batch_sweep   B in {1, 16, 256, 4096, 65536} on one GPU (BASELINE metric range); 65536 repeated three times
   wbc_qp        the batched whole-body inverse-dynamics QP at B = 65536
-  roofline      HBM classification of SURVEY.md 8d: algorithmic bytes B_io per solve x solves per launch /
-                kernel time (HIP events on the launch stream, non-overlapped launch) vs 8 TB/s
   cpu_baseline  the C oracle (a port, not CasADi/IPOPT) on the host cores this job really has (cgroup quota next to the
                 affinity mask), bounded sample, rank 0, N=1 -- plus SURVEY 8d's leg (a): one thread, one instance at a time
-  iterations / kkt quantiles of the timed batch (SURVEY 8d "Metric" row), per-rank step time and gather time at N > 1
 
 --seed S draws a fresh batch of the same distribution (default: the configuration's own seed).
 """
@@ -145,6 +151,55 @@ def cpu_baseline(spec, rec_all, threads=None, budget_s=15.0, single_budget_s=6.0
                       f"instances one at a time, {dt1:.1f} s; CasADi/IPOPT cannot run here (SURVEY 8c)"}
 
 
+DUMP_PER_INSTANCE_BYTES = 20 << 20   # x1_u0 + kkt + status + iterations of every instance, or of the sample beyond this
+DUMP_SOLUTION_BYTES = 40 << 20       # the sampled rows of the full primal solution
+DUMP_SOLUTION_ROWS = 4096
+DUMP_SAMPLE_SEED = 20251016
+
+
+def dump_sample(B, nsol):
+    """Input-order indices of the instances whose full solution is dumped: a fixed, seeded sample (every instance when
+    the batch is small enough), sorted."""
+    n = int(min(B, DUMP_SOLUTION_ROWS, DUMP_SOLUTION_BYTES // (8 * nsol)))
+    if n >= B:
+        return np.arange(B, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(B, size=n, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path, full, XU, rows, B_total, reduce_sum=None):
+    """Write what the last timed step returned, as float64 .npy files under `path` (at most 64 MB in all):
+      x1_u0, kkt, status, iterations  per instance, input order (the gathered (x_1, u_0, kkt, status, iters) of the step;
+                                      a seeded sample of instances when they would exceed DUMP_PER_INSTANCE_BYTES)
+      solution                        full primal solution (x_0..x_N, u_0..u_{N-1}) of a seeded sample of instances
+      instances, solution_instances   the input-order indices of those rows
+    `full`: (B_total, cols) gathered rows in input order; `XU`: this rank's (len(rows), nsol) solution, rows `rows`
+    (input-order indices); `reduce_sum`: sums a tensor over the ranks in place (None on one rank).  Returns the
+    {name: array} written (None on the ranks other than 0, which only take part in the reduction)."""
+    sol_idx = dump_sample(B_total, XU.shape[1])
+    # every instance in the sample lives on exactly one rank: scatter the local rows into place and sum over the ranks
+    pos = np.searchsorted(sol_idx, rows)
+    mine = (pos < sol_idx.shape[0]) & (sol_idx[np.minimum(pos, sol_idx.shape[0] - 1)] == rows)
+    sol = XU.new_zeros((sol_idx.shape[0], XU.shape[1]))
+    if mine.any():
+        sol[pos[mine]] = XU[np.nonzero(mine)[0]]
+    if reduce_sum is not None:
+        reduce_sum(sol)
+    if path is None:
+        return None
+    inst = np.arange(B_total, dtype=np.int64)
+    if B_total * full.shape[1] * 8 > DUMP_PER_INSTANCE_BYTES:
+        n = DUMP_PER_INSTANCE_BYTES // (full.shape[1] * 8)
+        inst = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED + 1).choice(B_total, size=n, replace=False)).astype(np.int64)
+    f = full[inst].cpu().numpy().astype(np.float64)
+    arrays = {"x1_u0": f[:, :-3], "kkt": f[:, -3], "status": f[:, -2], "iterations": f[:, -1],
+              "instances": inst.astype(np.float64), "solution": sol.cpu().numpy(),
+              "solution_instances": sol_idx.astype(np.float64)}
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return arrays
+
+
 def self_launch(n, argv, timeout_s=None):
     """Start the n ranks of `bench.py --gpus n` as child processes (one per GPU, rendezvous on 127.0.0.1) and
     return the worst exit code.  Runs in a parent that has not imported torch and never touches the GPU.  The parent
@@ -219,9 +274,17 @@ def main():
                     help="bare --gpus N launcher: seconds after which ranks still running are stopped (exit code 124)")
     ap.add_argument("--kernel", default="auto", choices=["auto", "single", "pair"],
                     help="cmpc_spec.kernel of the solver handles (auto = the library's choice by batch size)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the pipelined / warm-start / batch-sweep legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline: pipelined, warm start, batch sweep, seeds, whole-body QP, "
+                         "CPU baseline (off: set up, warm up, time the steps, print the line)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU legs")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the pipelined / warm-start / batch-sweep / seeds / whole-body QP legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.batch is None:
         args.batch = PER_GPU_BATCH[args.workload]
 
@@ -291,7 +354,9 @@ def main():
     rows = cdist.dealt_rows(order, world, rank)
     lo, hi = 0, int(rows.shape[0])                                 # (this rank's share: hi - lo instances)
     rec = torch.from_numpy(rec_all[rows].copy()).to(device)        # resident in HBM before timing
-    n_handles = max(2, args.streams)
+    S = max(1, args.streams)
+    extras = world == 1 and args.full and not args.no_extras
+    n_handles = max(2, S) if extras else S                          # the pipelined leg alternates over two handles
     solvers = [BatchedCentroidalMPC(spec, device=device) for _ in range(n_handles)]
     streams = [torch.cuda.Stream(device=device) for _ in range(n_handles)]
     outs = [torch.empty((hi - lo, spec.nsol), dtype=torch.float64, device=device) for _ in range(n_handles)]
@@ -340,13 +405,23 @@ def main():
             dist.all_reduce(t_max, op=dist.ReduceOp.MAX)
         return float(t_max.item()), full, el_local
 
-    S = max(1, args.streams)
     marks = []
     elapsed, full, el_local = timed(S, args.steps, args.warmup, marks=marks)
     # kernel time: AVERAGE over the timed launches (round 3 read the last launch only: 115 - 121 ms spread)
     k_ms = [m[0].elapsed_time(m[1]) for m in marks]
     g_ms = [m[2].elapsed_time(m[3]) for m in marks]
     kernel_ms = float(np.mean(k_ms))
+    if args.dump_outputs:
+        # before any other leg reuses the output buffers: what the last timed step returned
+        def reduce_sum(t):
+            if t.is_cuda and dist.get_backend() == "gloo":        # rehearsal path (ranks sharing one GPU): through the host
+                h = t.cpu()
+                dist.all_reduce(h)
+                t.copy_(h)
+            else:
+                dist.all_reduce(t)
+        dump_outputs(args.dump_outputs if rank == 0 else None, full, outs[(args.steps - 1) % S], rows, B_total,
+                     reduce_sum=reduce_sum if world > 1 else None)
 
     st = full[:, -2].to(torch.int32)
     it = full[:, -1]
@@ -420,7 +495,7 @@ def main():
                            "note": "ms_per_step_local = a rank's own steps before it waits for the others; gather_ms = HIP "
                                    "events around the all-gather on the launch stream (includes waiting for the slowest rank)"}
 
-    if world == 1 and not args.no_extras:
+    if extras:
         # --- independent batches pipelined over two streams
         el2, full2, _ = timed(2, args.steps, 2)
         c2 = float((full2[:, -2] == 0).double().mean().item())
@@ -476,7 +551,7 @@ def main():
                            "note": "same serial measurement as `value` on fresh batches of the same distribution; the first "
                                    "seed is the configuration's own (= `value`)"}
 
-    if world == 1 and not args.no_extras:
+    if extras:
         # --- the next row of the scope table: batched whole-body inverse-dynamics QP, B = 65536
         from cmpc_amd import wbc
         Bq, uniq = 65536, 1024
@@ -512,7 +587,7 @@ def main():
             result["wbc_qp"]["cpu_oracle_qps_per_s_one_core"] = nq / (time.perf_counter() - t0)
         del mats
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(spec, rec_all)
     if rank == 0:
         print(json.dumps(result))
