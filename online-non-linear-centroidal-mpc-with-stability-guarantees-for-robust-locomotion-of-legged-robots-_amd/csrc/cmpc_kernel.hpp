@@ -2444,6 +2444,8 @@ template <int NV, int NW = 1, bool PIPE = false> struct Solver {
     // ("the answer is the saved iterate, already written" rides in the verdict -- bit SAVED of `st` -- until the loop is left:
     // as a flag of its own it was one more vector register carried across the whole iteration, and the one spilled)
     constexpr int SAVED = 256;
+    // (and "no step could be computed from the iterate" -- see the end of the attempt)
+    constexpr int NOSTEP = 512;
     // cold scalars of the outer loop live in LDS (every lane reads the same word; written by every lane with the
     // same value, fenced by the phases in between)
     double &reg_last = R(D::oCOLD + 0), &kkt_best = R(D::oCOLD + 1), &kkt_saved = R(D::oCOLD + 2);
@@ -2479,13 +2481,16 @@ template <int NV, int NW = 1, bool PIPE = false> struct Solver {
       bool fail = false;
       const double mu_sweep = mu;               // barrier value the sweep's gradients are formed at
       const double rl = reg_last;               // (cold state: read once, ahead of the fences of the sweep)
+#ifdef CMPC_TEST_FAIL_ITER                     // (test builds only, never the HIP library's: a failed factorisation at a chosen iteration)
+      if (!resume && it == (CMPC_TEST_FAIL_ITER)) fail = true; else
+#endif
       while (!matrix_sweep(mu, reg, x0n2, er, it == 0)) {
         sync();
         if (reg == 0.0) reg = (rl == 0.0) ? 1e-4 : fmax(1e-20, rl / 3);
         else reg *= (rl == 0.0) ? 100.0 : 8.0;
         if (reg > 1e20) { fail = true; break; }
       }
-      if (fail) { st = CMPC_NUMERICAL; break; }
+      if (fail) { st = CMPC_NUMERICAL | NOSTEP; break; }
 #ifdef CMPC_DEBUG_FIRST_SWEEP                  // (diagnostic build, tools/slab_diff.py: leave the slab as the first matrix sweep wrote it)
       if (it == 0) break;
 #endif
@@ -2594,11 +2599,16 @@ template <int NV, int NW = 1, bool PIPE = false> struct Solver {
       }
     }
     bool use_saved = (st & SAVED) != 0;
+    const bool nostep = (st & NOSTEP) != 0;
     st &= SAVED - 1;
     // A resumed attempt that failed is followed by a plain one with the rest of the budget; an acceptable point it saved on
     // the way is not given up: it stays in `out`, its error is the level the plain attempt has to beat, and with no budget
     // left for a plain attempt it is the answer (see the oracle).
     const double ks_end = kkt_saved;
+    // No step from the last iterate (a factorisation that fails for every regularisation, or a NaN iterate: the sweep comes
+    // before the error check): an acceptable point saved on the way -- this attempt's own or the one it inherited -- is the
+    // answer, as at the cap, and stays in `out` (see the oracle).
+    if (nostep && ks_end <= acc_tol()) { st = CMPC_ACCEPTABLE; kkt = ks_end; use_saved = true; }
     const bool keep = resume && (st == CMPC_MAX_ITER || st == CMPC_NUMERICAL) && ks_end <= acc_tol();
     if (keep && !(it < sp.max_iter)) { st = CMPC_ACCEPTABLE; kkt = ks_end; use_saved = true; }
     if (!use_saved && !keep && (!PIPE || wv == 0)) write_solution(out);

@@ -883,6 +883,9 @@ static void solve_one_capped(const cmpc_spec *sp, const double *rec, const doubl
     double reg = 0.0;
     int fail = 0;
     int rb_;
+#ifdef CMPC_TEST_FAIL_ITER                 /* (test builds only, never the product target: a failed factorisation at a chosen iteration) */
+    if (!resume && it == (CMPC_TEST_FAIL_ITER)) fail = 1; else
+#endif
     while ((rb_ = riccati_backward(P, W, reg)) != 0) {
       st->waste += (double)(N - (-rb_ - 1) + 1) / (N + 1);   /* share of a sweep done before the failing stage */
       if (reg == 0.0) reg = (reg_last == 0.0) ? 1e-4 : fmax(1e-20, reg_last / 3);
@@ -890,7 +893,13 @@ static void solve_one_capped(const cmpc_spec *sp, const double *rec, const doubl
       ++st->n_reg;
       if (reg > 1e20) { fail = 1; break; }
     }
-    if (fail) { st->status = CMPC_NUMERICAL; break; }
+    if (fail) {
+      /* no step can be computed from this iterate: an acceptable point saved on the way (this attempt's own, or the one a
+       * failed resumed attempt left in `out`) is the answer, as at the cap -- `out` is not overwritten (round-5 advisor) */
+      if (kkt_saved <= acc_tol) { st->status = CMPC_ACCEPTABLE; kkt = kkt_saved; use_saved = 1; }
+      else st->status = CMPC_NUMERICAL;
+      break;
+    }
     if (reg > 0) reg_last = reg;
     riccati_forward(P, W);
     /* ---- slack / multiplier steps, fraction to the boundary ---- */

@@ -88,15 +88,16 @@ def nstate(s):
     return nsol(s) + (s.N + 1) * ((20 + 2 * s.nv) + 2 * (15 + 10 * s.nv) + 2) + 8
 
 
-def solve_batch_state(spec, recs, warm=None, state=None, nthreads=0, verbose=0):
-    """Closed-loop form: (out, state_out, status, iters, kkt); `state` = the previous tick's state_out (or None)."""
+def solve_batch_state(spec, recs, warm=None, state=None, nthreads=0, verbose=0, so=None):
+    """Closed-loop form: (out, state_out, status, iters, kkt); `state` = the previous tick's state_out (or None).
+    so: a ctypes handle of another build of the oracle (test variants compiled with a switch); default the shipped one."""
     recs = np.ascontiguousarray(np.atleast_2d(recs), dtype=np.float64)
     B = recs.shape[0]
     warm = None if warm is None else np.ascontiguousarray(warm, dtype=np.float64)
     state = None if state is None else np.ascontiguousarray(state, dtype=np.float64)
     out, state_out = np.zeros((B, nsol(spec))), np.zeros((B, nstate(spec)))
     st, it, kkt = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B)
-    rc = lib().cmpc_oracle_solve_batch_state(ctypes.byref(spec), B, _p(recs), _p(warm), _p(state), _p(out), _p(state_out),
+    rc = (lib() if so is None else so).cmpc_oracle_solve_batch_state(ctypes.byref(spec), B, _p(recs), _p(warm), _p(state), _p(out), _p(state_out),
                                              _p(st), _p(it), _p(kkt), int(nthreads), int(verbose))
     assert rc == 0
     return out, state_out, st, it, kkt

@@ -81,6 +81,11 @@ static inline cmpc_v4d emu_mfma(double a, double b, cmpc_v4d c) {
 #define CMPC_MFMA_F64(a, b, c) emu_mfma((a), (b), (c))
 #define CMPC_OPAQUE(x) do { } while (0)
 
+// Test-only switch of the solver source (tests/test_kkt_certificate.py): CMPC_EMU_FAIL_ITER=K makes the factorisation of
+// iteration K of a plain (not resumed) attempt report failure, the exit a singular KKT system or a NaN iterate takes.
+// Never defined by the HIP library's build.
+static int emu_fail_iter = -1;
+#define CMPC_TEST_FAIL_ITER emu_fail_iter
 #include "../../online-non-linear-centroidal-mpc-with-stability-guarantees-for-robust-locomotion-of-legged-robots-_amd/csrc/cmpc_kernel.hpp"
 
 template <int NV, int NW, bool PIPE = false>
@@ -125,6 +130,7 @@ extern "C" int cmpc_emu_solve_batch_state(const cmpc_spec *sp, int32_t B, const 
   const bool pair = sp->nv == 4 && getenv("CMPC_EMU_PAIR") && atoi(getenv("CMPC_EMU_PAIR")) == 1;
   const size_t nl = pair ? 2 * cmpc::Dims<4, 1, true>::LDS_DOUBLES : (sp->nv == 4) ? cmpc::Dims<4>::LDS_DOUBLES
                     : cmpc::Dims<8, 2>::LDS_DOUBLES;
+  emu_fail_iter = getenv("CMPC_EMU_FAIL_ITER") ? atoi(getenv("CMPC_EMU_FAIL_ITER")) : -1;
   const double fill = getenv("CMPC_EMU_FILL") ? atof(getenv("CMPC_EMU_FILL")) : 0.0;
   std::vector<double> scratch(nd, fill), lds(nl, fill);
   ka.scratch = scratch.data(); ka.scratch_stride = nd;
