@@ -140,6 +140,27 @@ int cmpc_solve_batch_state(cmpc_handle *h, int32_t B, const double *params, cons
                            const double *state_in, double *out_XU, double *state_out, int32_t *status,
                            int32_t *iters, double *kkt_res, void *stream);
 
+/*
+ * cmpc_solve_batch_state plus the first-stage feedback gain of every instance:
+ *   gain  [B][CMPC_NGAIN(nv)]  device, NOT NULL (a caller who wants no gain calls cmpc_solve_batch_state)
+ * G[b] = d(x_1, u_0)/dx0, the Jacobian of the returned X[:,1] and U[:,0] of instance b with respect to x0 = params[b][0:20],
+ * row-major [CMPC_NX + CMPC_NU(nv)][CMPC_NX]: rows x_1 (20), then u_0 (nu); one column per component of x0.  Every other
+ * record entry and the proximal centre (warm_XU) stay fixed.  It is the derivative of the barrier problem the solver solved
+ * last, at its final barrier value, taken at the point returned in out_XU (away from weakly active constraints: the
+ * active-set sensitivity of the NLP).  Between two solves a caller can track u_0 + G_u (x - x0).
+ * A whole row block of NaN means no gain: status 1 or 2, or a KKT system at the returned point that needs an inertia
+ * correction (its reduced Hessian is not positive definite, the derivative is not defined).  Every status-0 instance
+ * whose system needs none has a finite gain.
+ * Same semantics, queue order and kernel choice (cmpc_spec.kernel) as cmpc_solve_batch_state: out_XU, status, iters,
+ * kkt_res and state_out are bit for bit that call's; the gain variant of the kernel runs (cmpc_last_kernel_name names it).
+ * The first call on a handle allocates one saved iterate per slab (CMPC_NSTATE doubles each, not counted by
+ * cmpc_workspace_bytes): it synchronises the device and must not be made under stream capture.
+ */
+#define CMPC_NGAIN(nv) ((CMPC_NX + CMPC_NU(nv)) * CMPC_NX)
+int cmpc_solve_batch_gain(cmpc_handle *h, int32_t B, const double *params, const double *warm_XU,
+                          const double *state_in, double *out_XU, double *state_out, int32_t *status,
+                          int32_t *iters, double *kkt_res, double *gain, void *stream);
+
 /* Average kernel time (ms) of the last cmpc_solve_batch on this handle, measured with
  * HIP events on the launch stream; synchronises that stream. */
 int cmpc_last_kernel_ms(cmpc_handle *h, float *ms);

@@ -158,6 +158,59 @@ __global__ void __launch_bounds__(128, WPS) cmpc_solve_pair_kernel(cmpc::KArgs k
   }
 }
 
+// Gain variants (cmpc_solve_batch_gain): the loops above with Solver<..., GAIN = true> -- the solve is the same, and the
+// first-stage gain follows it (cmpc_kernel.hpp, Solver::gain_tail).  Kernels of their own, so that the plain ones are
+// left as they are.  gain [B][CMPC_NGAIN(nv)]; gbuf: the saved iterate of each workgroup (CMPC_NSTATE doubles).
+template <int NV, int NW>
+__global__ void __launch_bounds__(64 * NW, (NV == 4 ? CMPC_WAVES_PER_SIMD : 1)) cmpc_solve_gain_kernel(cmpc::KArgs ka, double *gain,
+                                                                                                        double *gbuf, int *ticket,
+                                                                                                        const int *__restrict__ order) {
+  using D = cmpc::Dims<NV, NW>;
+  __shared__ __attribute__((aligned(16))) double lds[D::LDS_DOUBLES];
+  __shared__ int next;
+  double *slab = ka.scratch + (size_t)blockIdx.x * ka.scratch_stride;
+  const size_t nrec = CMPC_NREC(ka.sp.N), nsol = CMPC_NSOL(ka.sp.N, NV), nstate = CMPC_NSTATE(ka.sp.N, NV);
+  for (;;) {
+    const int tid = (NW == 1) ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : (int)threadIdx.x;
+    if (tid == 0) next = atomicAdd(ticket, 1);
+    __syncthreads();
+    const int tk = next;
+    __syncthreads();
+    if (tk >= ka.B) break;
+    const int p = __builtin_amdgcn_readfirstlane(order[__builtin_amdgcn_readfirstlane(tk)]);
+    cmpc::Solver<NV, NW, false, true> s(ka, lds, slab, ka.recs + (size_t)p * nrec);
+    s.gain_out = gain + (size_t)p * CMPC_NGAIN(NV);
+    s.gbuf = cmpc::GArr{gbuf + (size_t)blockIdx.x * nstate};
+    s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr,
+            ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr, ka.out + (size_t)p * nsol, ka.status + p,
+            ka.iters + p, ka.kkt + p);
+  }
+}
+
+template <int NV, int WPS>
+__global__ void __launch_bounds__(128, WPS) cmpc_solve_pair_gain_kernel(cmpc::KArgs ka, double *gain, double *gbuf, int *ticket,
+                                                                        const int *__restrict__ order) {
+  using D = cmpc::Dims<NV, 1, true>;
+  __shared__ __attribute__((aligned(16))) double lds[2 * D::LDS_DOUBLES];
+  __shared__ int next;
+  double *slab = ka.scratch + (size_t)blockIdx.x * ka.scratch_stride;
+  const size_t nrec = CMPC_NREC(ka.sp.N), nsol = CMPC_NSOL(ka.sp.N, NV), nstate = CMPC_NSTATE(ka.sp.N, NV);
+  for (;;) {
+    if (threadIdx.x == 0) next = atomicAdd(ticket, 1);
+    __syncthreads();
+    const int tk = next;
+    __syncthreads();
+    if (tk >= ka.B) break;
+    const int p = __builtin_amdgcn_readfirstlane(order[__builtin_amdgcn_readfirstlane(tk)]);
+    cmpc::Solver<NV, 1, true, true> s(ka, lds, slab, ka.recs + (size_t)p * nrec);
+    s.gain_out = gain + (size_t)p * CMPC_NGAIN(NV);
+    s.gbuf = cmpc::GArr{gbuf + (size_t)blockIdx.x * nstate};
+    s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr,
+            ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr, ka.out + (size_t)p * nsol, ka.status + p,
+            ka.iters + p, ka.kkt + p);
+  }
+}
+
 // One workgroup per record (grid-stride over the batch), one lane per pair of output words: each
 // lane assembles two consecutive doubles and issues one 16-byte store, so a wavefront writes 1 KiB of
 // contiguous record per instruction; reads are gathers from tables that stay L2-resident
@@ -241,6 +294,7 @@ struct cmpc_handle {
   int *ticket = nullptr;                            // ORDER_COUNTERS words: the ticket and the counters of the queue order
   int *order = nullptr;                             // queue order of the last launch, order_cap entries
   int order_cap = 0;
+  double *gbuf = nullptr;                           // saved iterate of every slab (cmpc_solve_batch_gain; allocated by its first call)
   long long *prof = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
@@ -401,6 +455,7 @@ int cmpc_destroy(cmpc_handle *h) {
   if (h->scratch) (void)hipFree(h->scratch);
   if (h->ticket) (void)hipFree(h->ticket);
   if (h->order) (void)hipFree(h->order);
+  if (h->gbuf) (void)hipFree(h->gbuf);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
   if (h->ev1) (void)hipEventDestroy(h->ev1);
   delete h;
@@ -412,9 +467,12 @@ int cmpc_solve_batch(cmpc_handle *h, int32_t B, const double *params, const doub
   return cmpc_solve_batch_state(h, B, params, warm_XU, nullptr, out_XU, nullptr, status, iters, kkt_res, stream);
 }
 
-int cmpc_solve_batch_state(cmpc_handle *h, int32_t B, const double *params, const double *warm_XU, const double *state_in,
-                           double *out_XU, double *state_out, int32_t *status, int32_t *iters, double *kkt_res,
-                           void *stream) {
+}  // extern "C"
+
+// cmpc_solve_batch_state and cmpc_solve_batch_gain: gain == nullptr launches the plain kernels
+static int solve_batch(cmpc_handle *h, int32_t B, const double *params, const double *warm_XU, const double *state_in,
+                       double *out_XU, double *state_out, int32_t *status, int32_t *iters, double *kkt_res, double *gain,
+                       void *stream) {
   if (!h) return fail(nullptr, "cmpc_solve_batch: null handle");
   if (B < 0) return fail(h, "cmpc_solve_batch: negative batch");
   if (B == 0) return 0;
@@ -453,7 +511,22 @@ int cmpc_solve_batch_state(cmpc_handle *h, int32_t B, const double *params, cons
   const bool pair = h->spec.nv == 4 && B <= h->pair_max_batch;   // the batch does not fill the GPU for long: two waves per instance
   const int launch_grid = pair ? (B < h->pair_grid ? B : h->pair_grid) : grid;
   if (launch_grid > h->slabs) return fail(h, "cmpc_solve_batch: launch grid exceeds the slabs of the handle");
-  if (pair) {
+  if (gain) {
+    if (pair) {
+      const dim3 pg(launch_grid);
+#ifdef CMPC_DEV_KNOBS
+      if (h->pair_per_cu < 3) { hipLaunchKernelGGL((cmpc_solve_pair_gain_kernel<4, 1>), pg, dim3(128), 0, st, ka, gain, h->gbuf, h->ticket, h->order); h->last_kernel = "cmpc_solve_pair_gain_kernel<4, 1>"; }
+      else
+#endif
+      { hipLaunchKernelGGL((cmpc_solve_pair_gain_kernel<4, 2>), pg, dim3(128), 0, st, ka, gain, h->gbuf, h->ticket, h->order); h->last_kernel = "cmpc_solve_pair_gain_kernel<4, 2>"; }
+    } else if (h->spec.nv == 4) {
+      hipLaunchKernelGGL((cmpc_solve_gain_kernel<4, 1>), dim3(grid), dim3(64), 0, st, ka, gain, h->gbuf, h->ticket, h->order);
+      h->last_kernel = "cmpc_solve_gain_kernel<4, 1>";
+    } else {
+      hipLaunchKernelGGL((cmpc_solve_gain_kernel<8, cmpc::WAVES_NV8>), dim3(grid), dim3(64 * cmpc::WAVES_NV8), 0, st, ka, gain, h->gbuf, h->ticket, h->order);
+      h->last_kernel = "cmpc_solve_gain_kernel<8, 2>";
+    }
+  } else if (pair) {
     const dim3 pg(launch_grid);
 #ifdef CMPC_DEV_KNOBS
     if (h->pair_per_cu < 3) { hipLaunchKernelGGL((cmpc_solve_pair_kernel<4, 1>), pg, dim3(128), 0, st, ka, h->ticket, h->order); h->last_kernel = "cmpc_solve_pair_kernel<4, 1>"; }
@@ -471,6 +544,27 @@ int cmpc_solve_batch_state(cmpc_handle *h, int32_t B, const double *params, cons
   HIP_TRY(h, hipEventRecord(h->ev1, st));
   h->timed = true;
   return 0;
+}
+
+extern "C" {
+
+int cmpc_solve_batch_state(cmpc_handle *h, int32_t B, const double *params, const double *warm_XU, const double *state_in,
+                           double *out_XU, double *state_out, int32_t *status, int32_t *iters, double *kkt_res,
+                           void *stream) {
+  return solve_batch(h, B, params, warm_XU, state_in, out_XU, state_out, status, iters, kkt_res, nullptr, stream);
+}
+
+int cmpc_solve_batch_gain(cmpc_handle *h, int32_t B, const double *params, const double *warm_XU, const double *state_in,
+                          double *out_XU, double *state_out, int32_t *status, int32_t *iters, double *kkt_res, double *gain,
+                          void *stream) {
+  if (!h) return fail(nullptr, "cmpc_solve_batch_gain: null handle");
+  if (!gain) return fail(h, "cmpc_solve_batch_gain: null gain (use cmpc_solve_batch_state for a solve without one)");
+  if (B > 0 && !h->gbuf) {                       // once per handle; hipMalloc synchronises the device
+    DeviceGuard guard(h->device);
+    if (!guard.ok) return fail(h, "cmpc_solve_batch_gain: cannot select the handle's device");
+    HIP_TRY(h, hipMalloc(&h->gbuf, (size_t)h->slabs * CMPC_NSTATE(h->spec.N, h->spec.nv) * sizeof(double)));
+  }
+  return solve_batch(h, B, params, warm_XU, state_in, out_XU, state_out, status, iters, kkt_res, gain, stream);
 }
 
 int cmpc_last_kernel_ms(cmpc_handle *h, float *ms) {

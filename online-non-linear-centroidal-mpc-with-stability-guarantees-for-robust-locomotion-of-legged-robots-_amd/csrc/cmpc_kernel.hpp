@@ -185,6 +185,16 @@ constexpr bool COLD_ROLLOUT = true;
 constexpr int RESUME_RECENTRE_ITERS = 20;
 // waves per instance of the 8-vertex solver (Solver<8, WAVES_NV8>; the 4-vertex one is a single wave)
 constexpr int WAVES_NV8 = 2;
+// the gain's sweep (Solver::gain_tail) weighs an inequality row with min(z/s, cap): at the final barrier value a hard row's
+// z/s reaches 1e18, and a stage block that carries it loses ~eps z/s |grad g|^2 of its other curvature to rounding (1e-3 of
+// the gain, measured); capped, the row stays hard (its share of the derivative moves by ~c / cap, c the curvature it
+// competes with) and the block keeps its digits.  The foot box rows get a cap of their own: the position a landing foot
+// is pinned to is handed back through the swing stages, whose only curvature is the proximal weight over delta^2
+// (1e-2 at mpc_rate 10), as P - P^2 d^2 / (prox + d^2 P) -- a difference of two numbers of the size of the cap.  Measured
+// on the host emulation: with 1e12 that cost 1.4e-2 of the gain on a rate-10 instance, 4e-4 with 1e10;
+// below ~1e10 the other hard rows a foot position competes with (curvature ~4e6) show through instead.
+constexpr double GAIN_SIG_CAP = 1e12;
+constexpr double GAIN_SIG_CAP_BOX = 2e10;
 
 #ifndef CMPC_NO_DEVICE_CODE
 #include "cmpc_lds_asm.hpp"
@@ -415,7 +425,10 @@ struct GArr {
 // of the other; the cost-to-go P, its gradient and the cold scalars live in image 0 only.  Same arithmetic in the same
 // order as the single wave: results are bit for bit those of Solver<NV, 1>.  For batches that do not fill the GPU (the
 // reference's own use is ONE instance per tick, code/simulation.py:203-204): an instance finishes ~1.4x sooner.
-template <int NV, int NW = 1, bool PIPE = false> struct Solver {
+// GAIN: the variant behind cmpc_solve_batch_gain (include/cmpc.h).  It solves exactly as the plain solver does (every
+// line it adds is behind `if constexpr (GAIN)`) and then forms the first-stage gain d(x_1, u_0)/dx0 at the returned point
+// (Solver::gain_tail).
+template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false> struct Solver {
   using D = Dims<NV, NW, PIPE>;
   // PIPE: words behind the two LDS images.  [0..5] error measures, [6] ap, [7] ad, [8..9] factorisation verdict of the
   // sweep step in hand (by step parity), [16 ..): du_k of the forward sweep by stage parity (read by the slack wave)
@@ -449,6 +462,11 @@ template <int NV, int NW = 1, bool PIPE = false> struct Solver {
   double piv_min = PIV_MIN;  // pivot acceptance threshold of the current sweep
   GArr st_in{nullptr};       // solver state resumed from (null: cold rule for slacks / multipliers)
   long long tprof[28] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
+  // GAIN only: this instance's gain ([CMPC_NX + NU][CMPC_NX], row-major) and the slot's copy of the saved iterate
+  // (CMPC_NSTATE layout; written wherever the solver saves a point to `out`)
+  double *gain_out = nullptr;
+  GArr gbuf{nullptr};
+  bool gain_sweep = false;   // the sweep of gain_tail: row weights capped (GAIN_SIG_CAP, GAIN_SIG_CAP_BOX)
 
   CMPC_DEV Solver(const KArgs &a, double *l, double *g, const double *r)
       : ka(a), sp(a.sp), lds(l), ldsR(l), gs{g}, rec{const_cast<double *>(r)}, N(a.sp.N), lane(CMPC_LANE) {
@@ -1687,7 +1705,8 @@ template <int NV, int NW = 1, bool PIPE = false> struct Solver {
         gsl[k * NI + r] = s; gz[k * NI + r] = z;
       }
       if (act) {
-        const double sg = z / s;
+        double sg = z / s;
+        if constexpr (GAIN) { if (gain_sweep) sg = fmin(sg, (r >= R_BOX && r < R_FRIC) ? GAIN_SIG_CAP_BOX : GAIN_SIG_CAP); }
         L(D::oW0 + r) = sg; L(D::oW1 + r) = sg * (g + s); L(D::oW2 + r) = 1.0 / s;
         er.e_p = fmax(er.e_p, fabs(g + s));
         er.e_c = fmax(er.e_c, fabs(s * z)); er.e_cmu = fmax(er.e_cmu, fabs(s * z - mu));
@@ -2411,6 +2430,156 @@ template <int NV, int NW = 1, bool PIPE = false> struct Solver {
   }
 
   // ---------------------------------------------------------------------------------------
+  // First-stage gain (GAIN variants only): G = d(x_1, u_0)/dx0 of the barrier problem the solver solved last, at the point
+  // it returned ("First-stage gain").  With x_0 fixed to x0, the Riccati factor of stage 0 gives
+  //   du_0/dx0 = -Lambda^-T (Ls' E + Lambda^-1 R),   dx_1/dx0 = A_0 E + B_0 du_0/dx0,
+  // E = the first CMPC_NX columns of the identity (x0 has no carried-force part).  R collects what of the dependence on
+  // x0 the stage blocks do not carry, because x_0 is data in the sweep:
+  //   * the Lyapunov row of stage 0 depends on c_0, v_0, theta_0, but its gradient and curvature in the state columns of
+  //     stage 0 are left out of the block (build_H_row, stage_ineq: k >= 1) -- sigma_L al_u al_x' + z_L d2g/du dx;
+  //   * the momentum-contraction row of stage 1 reads hw_0 from the record header: d/dx0 of its condensed gradient,
+  //     -4 sigma_H hw_1 hw_0', enters the cost-to-go gradient of stage 1 (state part only, so p_1 moves by it and l_1 does
+  //     not) and reaches stage 0 through B_0'.
+  // Every factor comes from the slab the matrix sweep at the returned point left (stage 0: Lambda, Ls, the dense rows of
+  // [B A]) and from the iterate arrays; the right-hand sides are held one row of R per lane (20 registers).  One wave, one
+  // fixed order: the one-wave and the pair kernels give the same bits.  good = false writes NaN.
+  CMPC_DEV void gain_step(bool good) {
+    constexpr int G = CMPC_NX;
+    const GArr gout{gain_out};
+    if (!good) {
+      const double nanv = __builtin_nan("");
+      for (int e = lane; e < (CMPC_NX + NU) * G; e += 64) gout[e] = nanv;
+      return;
+    }
+    const GArr st0 = stage(0);
+    const double d = SPD(delta), m = rec[20], k1 = SPD(k1), k2 = SPD(k2);
+    const double gm0 = rec[24 + 17], gm1 = rec[24 + 18];
+    // Lyapunov row of stage 0 (stage_ineq's expressions)
+    double z2[3], gz1[3], gz2[3];
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      double fl = 0.0, fr = 0.0;
+#pragma unroll
+      for (int v = 0; v < NV; ++v) { fl += gu[3 * v + a]; fr += gu[3 * (NV + v) + a]; }
+      const double grav = (a == 2) ? -SPD(g) : 0.0, V = (gm0 * fl + gm1 * fr) / m;
+      const double z1 = gx[a] + d * gx[3 + a] - rec[24 + a];
+      z2[a] = k1 * z1 + gx[3 + a] + d * (grav + V) - rec[24 + 3 + a];
+      const double un = -(k1 + k2) * z2[a] + k1 * k1 * z1 - grav + rec[24 + 6 + a] - gx[9 + a] / m;
+      gz1[a] = -2 * k1 * z1 + z2[a] - k1 * k1 * z2[a];
+      gz2[a] = -2 * k2 * z2[a] + z1 + (V - un) + (k1 + k2) * z2[a];
+    }
+    const double zL = gz[R_LYAP], sigL = fmin(zL / gsl[R_LYAP], GAIN_SIG_CAP);
+    const double sigH = fmin(gz[NI + R_HWC] / gsl[NI + R_HWC], GAIN_SIG_CAP);
+    const double a1[4] = {1, d, 0, 0}, a2[4] = {k1, k1 * d + 1, 0, d}, aS[4] = {0, 0, 1.0 / m, 1};
+    auto hq3 = [&](int p) {
+      return -2 * k1 * a1[p] * a1[3] + 2 * k1 * a2[p] * a2[3] + (1 - k1 * k1) * (a1[p] * a2[3] + a2[p] * a1[3]) +
+             a2[p] * aS[3] + aS[p] * a2[3];
+    };
+    // ---- R, one row per lane (lanes < NU)
+    const int jc = (lane < NU) ? lane : 0;
+    const bool jf = lane < 6 * NV;
+    const int ja = jc % 3;
+    const double gj = (((jc / 3) / NV) != 0) ? gm1 : gm0;
+    const double alu = jf ? gj * d / m * gz2[ja] + gj / m * z2[ja] : 0.0;
+    const double hb = -4 * sigH * (st0[D::gGH + jc] * gx[NXA + 6] + st0[D::gGH + D::GHS + jc] * gx[NXA + 7] +
+                                   st0[D::gGH + 2 * D::GHS + jc] * gx[NXA + 8]);
+    double rr[G];
+#pragma unroll
+    for (int c = 0; c < G; ++c) {
+      const int t = (c < 3) ? 0 : (c < 6) ? 1 : (c >= 9 && c < 12) ? 2 : -1, ax = c % 3;
+      const double alx = (t == 0) ? gz1[ax] + k1 * gz2[ax] : (t == 1) ? d * gz1[ax] + (k1 * d + 1) * gz2[ax]
+                       : (t == 2) ? z2[ax] / m : 0.0;
+      double v = sigL * alu * alx;
+      if (t >= 0 && jf && ja == ax) v += zL * hq3(t) / m * gj;
+      if (c >= 6 && c < 9) v += hb * rec[c];
+      rr[c] = (lane < NU) ? v : 0.0;
+    }
+    // ---- Y = Lambda^-1 R (forward substitution, column j of Lambda against the rows below it)
+    double y[G];
+#pragma unroll
+    for (int c = 0; c < G; ++c) y[c] = 0.0;
+#pragma unroll 1
+    for (int j = 0; j < NU; ++j) {
+      const double dinv = 1.0 / st0[D::gM + tri(j) + j], lij = st0[D::gM + tri(jc) + j];
+#pragma unroll
+      for (int c = 0; c < G; ++c) {
+        const double yj = CMPC_BCAST(rr[c] * dinv, j);
+        if (lane == j) y[c] = yj;
+        else if (lane > j && lane < NU) rr[c] -= lij * yj;
+      }
+    }
+    // ---- du_0/dx0 = -Lambda^-T (Ls' E + Y) (back substitution, as the forward sweep's)
+#pragma unroll
+    for (int c = 0; c < G; ++c) rr[c] = (lane < NU) ? -(st0[D::gM + tri(NU + c) + jc] + y[c]) : 0.0;
+#pragma unroll 1
+    for (int j = NU - 1; j >= 0; --j) {
+      const double dinv = 1.0 / st0[D::gM + tri(j) + j], lji = st0[D::gM + tri(j) + jc];
+#pragma unroll
+      for (int c = 0; c < G; ++c) {
+        const double dj = CMPC_BCAST(rr[c] * dinv, j);
+        if (lane == j) y[c] = dj;
+        else if (lane < j) rr[c] -= lji * dj;
+      }
+    }
+    if (lane < NU) {
+#pragma unroll
+      for (int c = 0; c < G; ++c) gout[(CMPC_NX + lane) * G + c] = y[c];
+    }
+    // ---- dx_1/dx0 = [B A]_0 (du_0/dx0; E), one row of x_1 per lane (lanes < CMPC_NX), column by column of the stage's
+    // column lists (the dense rows from the slab)
+    double acc[G];
+#pragma unroll
+    for (int c = 0; c < G; ++c) acc[c] = 0.0;
+    const double *gh0 = &st0[D::gGH];
+#pragma unroll 1
+    for (int col = 0; col < NZ; ++col) {
+      int r[6];
+      double gv[6];
+      column_list(col, r, gv, gh0, gm0, gm1, m);     // (reads gh0[col] as row 6; rows 7, 8 at the slab's stride:)
+      gv[2] = st0[D::gGH + D::GHS + col]; gv[3] = st0[D::gGH + 2 * D::GHS + col];
+      double cf = 0.0;                               // this lane's row of the column
+#pragma unroll
+      for (int n = 0; n < 6; ++n) cf += (r[n] == lane && (n == 0 ? col >= NU : true)) ? gv[n] : 0.0;
+      if (col < NU) {
+        const int cu = CMPC_UNIFORM_INT(col);
+#pragma unroll
+        for (int c = 0; c < G; ++c) { const double du = CMPC_BCAST(y[c], cu); acc[c] += cf * du; }
+      } else {
+        const int sx = col - NU;
+        if (sx < G) acc[sx] += cf;
+      }
+    }
+    if (lane < CMPC_NX) {
+#pragma unroll
+      for (int c = 0; c < G; ++c) gout[lane * G + c] = acc[c];
+    }
+  }
+
+  // GAIN: after the verdict.  The factorisation the solve left in the slab may belong to another point than the one
+  // returned (a saved point: status 3, or 0 after a polish that lost ground), so the iterate that was returned is entered
+  // again -- the saved copy through the resume path, the last iterate as it stands -- and ONE matrix sweep is run at it
+  // (its matrices do not depend on the barrier value; no inertia correction: a sweep that needs one means the reduced
+  // Hessian is not positive definite there, and the gain is NaN).  The sweep weighs the inequality rows with z/s capped at
+  // GAIN_SIG_CAP / GAIN_SIG_CAP_BOX (see there).  Status 1 / 2: NaN.
+  CMPC_DEV void gain_tail(int st, bool saved, const double *warm) {
+    const bool usable = st == CMPC_CONVERGED || st == CMPC_ACCEPTABLE;
+    bool good = false;
+    if (usable) {
+      if (saved) {
+        st_in = gbuf;
+        if (!PIPE || wv == 0) initial_point(gbuf.p, warm, true);
+        if constexpr (PIPE) pair_sync(); else gsync();
+      }
+      Err er;
+      gain_sweep = true;
+      good = matrix_sweep(sp.tol, 0.0, 0.0, er, false);
+      if constexpr (PIPE) pair_sync(); else gsync();
+    }
+    if (wv == 0) gain_step(good);
+    if constexpr (PIPE) pair_sync(); else gsync();
+  }
+
+  // ---------------------------------------------------------------------------------------
   CMPC_DEV void solve(const double *warm, const double *state_in, double *state_out, double *out, int32_t *status,
                       int32_t *iters, double *kkt_out) {
     // (the tolerance where it is used, from its scalar register: as a local it was a vector register carried through the
@@ -2427,6 +2596,7 @@ template <int NV, int NW = 1, bool PIPE = false> struct Solver {
       if (resume) st_in = GArr{const_cast<double *>(state_in)};
     }
     int st = CMPC_MAX_ITER, it = 0, spent = 0;
+    bool ret_saved = false;                     // (GAIN) the answer is the saved iterate
     // iteration budget of an attempt: sp.max_iter - spent (both attempts together stay within max_iter)
     double kkt = INFINITY;
     // at most two attempts: a resumed solve that gets nowhere (the state was too far from this tick's problem) is
@@ -2524,7 +2694,11 @@ template <int NV, int NW = 1, bool PIPE = false> struct Solver {
       }
       if (polish < 0) {
         // best acceptable iterate so far (see the oracle): whatever ends the run, it is what is returned
-        if (kkt <= save_tol() && kkt < ks) { if (!PIPE || wv == 0) write_solution(out); ks = kkt; kkt_saved = kkt; }
+        if (kkt <= save_tol() && kkt < ks) {
+          if (!PIPE || wv == 0) write_solution(out);
+          if constexpr (GAIN) { if (!PIPE || wv == 0) write_state(gbuf.p, mu); }   // (the whole saved iterate)
+          ks = kkt; kkt_saved = kkt;
+        }
         if (kkt <= tol_()) {
           // (the tolerance was met from a level >= MU_WARM: same snapshot)
           if (state_out && mu >= MU_WARM && unsnapped) { if (!PIPE || wv == 0) write_state(state_out, mu); snapped = 1.0; }
@@ -2612,6 +2786,7 @@ template <int NV, int NW = 1, bool PIPE = false> struct Solver {
     const bool keep = resume && (st == CMPC_MAX_ITER || st == CMPC_NUMERICAL) && ks_end <= acc_tol();
     if (keep && !(it < sp.max_iter)) { st = CMPC_ACCEPTABLE; kkt = ks_end; use_saved = true; }
     if (!use_saved && !keep && (!PIPE || wv == 0)) write_solution(out);
+    if constexpr (GAIN) ret_saved = use_saved;
     // (the verdict is the same in every lane; said so, the attempt loop is a uniform loop and what it carries -- the
     // iterations spent -- lives in a scalar register instead of a spilled vector one)
     const int again = CMPC_UNIFORM_INT((int)(resume && (st == CMPC_MAX_ITER || st == CMPC_NUMERICAL) && it < sp.max_iter));
@@ -2624,6 +2799,7 @@ template <int NV, int NW = 1, bool PIPE = false> struct Solver {
       // (first spare word of the state: what this solve took -- the next launch queues its instances by it)
       if (state_out) GArr{state_out}[D::state_mu(N) + 1] = (double)(it + spent);
     }
+    if constexpr (GAIN) gain_tail(st, ret_saved, warm);
 #if defined(CMPC_PROFILE) && !defined(CMPC_HOST_EMU)
     if (lane == 0 && ka.prof)
       for (int i = 0; i < 28; ++i) atomicAdd((unsigned long long *)&ka.prof[i], (unsigned long long)tprof[i]);

@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import capi
-from .problem import ProblemSpec, to_cspec
+from .problem import NX, ProblemSpec, to_cspec
 
 # per-instance outcome (include/cmpc.h): 3 = stopped short of `tol` with a KKT error within `acc_tol`
 # (IPOPT's "Solved To Acceptable Level", which CasADi's Opti.solve() returns without raising)
@@ -69,6 +69,9 @@ class BatchedCentroidalMPC:
         ``state`` (B, nstate) = the previous tick's ``state_out`` (``new_state()`` for the first tick), and this
         tick's state is written to ``state_out`` (a different tensor): ``cmpc_solve_batch_state``.
         """
+        return self._solve(records, warm, out, state, state_out, None)
+
+    def _solve(self, records, warm, out, state, state_out, gain):
         sp = self.spec
         if not (records.is_cuda and records.dtype == torch.float64 and records.is_contiguous()):
             raise ValueError("records must be a contiguous fp64 CUDA tensor")
@@ -97,16 +100,40 @@ class BatchedCentroidalMPC:
         if B == 0:
             return out, status, iters, kkt
         stream = torch.cuda.current_stream(records.device).cuda_stream
-        rc = self._lib.cmpc_solve_batch_state(self._h, B, records.data_ptr(),
-                                              warm.data_ptr() if warm is not None else None,
-                                              state.data_ptr() if state is not None else None,
-                                              out.data_ptr(),
-                                              state_out.data_ptr() if state_out is not None else None,
-                                              status.data_ptr(), iters.data_ptr(), kkt.data_ptr(),
-                                              ctypes.c_void_p(stream))
+        args = (self._h, B, records.data_ptr(), warm.data_ptr() if warm is not None else None,
+                state.data_ptr() if state is not None else None, out.data_ptr(),
+                state_out.data_ptr() if state_out is not None else None,
+                status.data_ptr(), iters.data_ptr(), kkt.data_ptr())
+        if gain is None:
+            rc = self._lib.cmpc_solve_batch_state(*args, ctypes.c_void_p(stream))
+        else:
+            rc = self._lib.cmpc_solve_batch_gain(*args, gain.data_ptr(), ctypes.c_void_p(stream))
         if rc != 0:
             raise RuntimeError("cmpc_solve_batch failed: " + self._lib.cmpc_last_error(self._h).decode())
         return out, status, iters, kkt
+
+    def solve_with_gain(self, records, warm=None, out=None, state=None, state_out=None, gain=None):
+        """``solve`` plus the first-stage feedback gain: (XU, status, iters, kkt, G), G (B, 20 + nu, 20) on the GPU.
+
+        G[b] = d(x_1, u_0)/dx0 of instance b: rows X[:,1] (20) then U[:,0] (nu), one column per component of
+        x0 = records[b, 0:20]; every other record entry and the proximal centre ``warm`` stay fixed.  XU, status,
+        iters, kkt and ``state_out`` are bit for bit those of ``solve``.  Rows of NaN: no gain (status 1 / 2, or a KKT
+        system at the returned point that needs an inertia correction) -- include/cmpc.h, INTEGRATION.md.
+        ``cmpc_solve_batch_gain``; its first call on a handle synchronises the device (not under graph capture).
+        """
+        sp = self.spec
+        if not (isinstance(records, torch.Tensor) and records.dim() == 2):
+            raise ValueError(f"records must be a contiguous fp64 CUDA tensor of shape (B, {sp.nrec})")
+        shape = (records.shape[0], NX + sp.nu, NX)
+        if gain is None:
+            if not records.is_cuda:
+                raise ValueError("records must be a contiguous fp64 CUDA tensor")
+            gain = torch.empty(shape, dtype=torch.float64, device=records.device)
+        elif not (gain.is_cuda and gain.dtype == torch.float64 and gain.is_contiguous() and tuple(gain.shape) == shape
+                  and gain.device == self.device):
+            raise ValueError(f"gain must be a contiguous fp64 CUDA tensor of shape {shape}")
+        out, status, iters, kkt = self._solve(records, warm, out, state, state_out, gain)
+        return out, status, iters, kkt, gain
 
     def new_state(self, B):
         """An empty solver state for B instances (barrier word 0 = "no state": the first tick starts cold)."""
