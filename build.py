@@ -86,6 +86,18 @@ def build_emu_gain(force=False):
     return out
 
 
+def build_emu_consts(force=False):
+    """Host emulation of the solver with per-instance constants (tests/emu/cmpc_emu_consts.cpp): test harness only."""
+    src = os.path.join(ROOT, "tests", "emu", "cmpc_emu_consts.cpp")
+    out = os.path.join(ROOT, "tests", "emu", "libcmpc_emu_consts.so")
+    deps = [src, os.path.join(ROOT, "tests", "emu", "cmpc_emu.cpp"), os.path.join(PKG, "csrc", "cmpc_kernel.hpp"),
+            os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp"),
+            os.path.join(ROOT, "include", "cmpc.h")]
+    if force or _newer(out, deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-o", out, src])
+    return out
+
+
 def build_device_unit(force=False):
     """GPU-tier unit harness for the device-only primitives (tests/gpu_unit): never loaded by the package."""
     src = os.path.join(ROOT, "tests", "gpu_unit", "cmpc_device_unit.hip")
@@ -119,5 +131,6 @@ if __name__ == "__main__":
     print(build_oracle(force))
     print(build_emu(force))
     print(build_emu_gain(force))
+    print(build_emu_consts(force))
     print(build_device_unit(force))
     print(build_tools(force))

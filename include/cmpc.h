@@ -29,7 +29,8 @@ extern "C" {
 #define CMPC_NX 20            /* reference state size (:164-166)                      */
 #define CMPC_MAX_N 64         /* horizon limit of this build                          */
 
-/* Problem constants shared by a batch.  Defaults = the literals of the reference. */
+/* Problem constants shared by a batch (cmpc_solve_batch_consts: the eighteen doubles from delta to relax per instance).
+ * Defaults = the literals of the reference. */
 typedef struct cmpc_spec {
   int32_t N;                  /* horizon, params['N'] (:10)                           */
   int32_t nv;                 /* contact vertices per foot: 4 (reference, :55-60) or 8 */
@@ -160,6 +161,31 @@ int cmpc_solve_batch_state(cmpc_handle *h, int32_t B, const double *params, cons
 int cmpc_solve_batch_gain(cmpc_handle *h, int32_t B, const double *params, const double *warm_XU,
                           const double *state_in, double *out_XU, double *state_out, int32_t *status,
                           int32_t *iters, double *kkt_res, double *gain, void *stream);
+
+/*
+ * cmpc_solve_batch_state with per-instance problem constants: tuning sweeps over the gains or weights, domain randomisation
+ * of the foot geometry / height limit / contact box / gravity, and mixed fleets (nominal, payload, mpc_rate 10) in ONE launch.
+ *   consts  [B][CMPC_NCONST]  device, NOT NULL: one row of doubles per instance, in the field order of cmpc_spec:
+ *             [0] delta  [1] g  [2] k1  [3] k2  [4] w_rate  [5] w_hw  [6] w_cxy  [7] w_cz_const  [8] w_foot  [9] w_force
+ *             [10] cz_max  [11..13] box[3]  [14] foot_length  [15] foot_width  [16] prox  [17] relax
+ * Instance b is solved with the handle's spec in which these eighteen fields are replaced by consts[b]; every other
+ * argument is cmpc_solve_batch_state's.  N, nv, max_iter, tol, acc_tol and kernel stay the handle's (tol and acc_tol on
+ * purpose: the levels the solver derives from them are computed on the host and passed as kernel arguments).
+ * A row equal to cmpc_spec_consts(spec) gives bit for bit what cmpc_solve_batch_state gives for that instance, and an
+ * instance's result does not depend on the rows of the others.  The "consts" variant of the kernel runs
+ * (cmpc_last_kernel_name names it, e.g. "cmpc_solve_consts_kernel<4, 1>"); it reads the row by scalar loads.
+ * Rows are checked on the device, never by a host synchronisation: a row with a non-finite entry, with delta, g, cz_max,
+ * foot_length, foot_width or a box entry <= 0, or with a weight (w_*), prox or relax < 0 makes THAT instance return
+ * CMPC_NUMERICAL (iters 0, kkt_res +inf, out_XU all NaN, no solver state); the other instances are untouched.
+ * Asynchronous; may run under stream capture under the conditions of cmpc_solve_batch_state (B no larger than in an
+ * earlier call on the handle).
+ */
+#define CMPC_NCONST 18
+/* Host helper: the row that reproduces `spec` (row[i] as listed above). */
+void cmpc_spec_consts(const cmpc_spec *spec, double row[CMPC_NCONST]);
+int cmpc_solve_batch_consts(cmpc_handle *h, int32_t B, const double *params, const double *consts, const double *warm_XU,
+                            const double *state_in, double *out_XU, double *state_out, int32_t *status, int32_t *iters,
+                            double *kkt_res, void *stream);
 
 /* Average kernel time (ms) of the last cmpc_solve_batch on this handle, measured with
  * HIP events on the launch stream; synchronises that stream. */

@@ -15,7 +15,8 @@ LIB_PATH = os.environ.get("CMPC_LIB_PATH") or os.path.join(_HERE, "libcmpc_amd.s
 
 #: every symbol include/cmpc.h declares
 SYMBOLS = ("cmpc_default_spec", "cmpc_create", "cmpc_destroy", "cmpc_workspace_bytes",
-           "cmpc_solve_batch", "cmpc_solve_batch_state", "cmpc_solve_batch_gain", "cmpc_last_kernel_ms", "cmpc_last_kernel_name", "cmpc_last_error",
+           "cmpc_solve_batch", "cmpc_solve_batch_state", "cmpc_solve_batch_gain", "cmpc_solve_batch_consts", "cmpc_spec_consts",
+           "cmpc_last_kernel_ms", "cmpc_last_kernel_name", "cmpc_last_error",
            "cmpc_version",
            "cmpc_tables_create", "cmpc_tables_destroy", "cmpc_build_records",
            "cmpc_tables_set_plan_slots", "cmpc_build_records_planned")
@@ -50,6 +51,10 @@ def load():
     lib.cmpc_solve_batch_state.restype = ctypes.c_int
     lib.cmpc_solve_batch_gain.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cmpc_solve_batch_gain.restype = ctypes.c_int
+    lib.cmpc_solve_batch_consts.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cmpc_solve_batch_consts.restype = ctypes.c_int
+    lib.cmpc_spec_consts.argtypes = [c_spec_p, ctypes.POINTER(ctypes.c_double)]
+    lib.cmpc_spec_consts.restype = None
     lib.cmpc_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]
     lib.cmpc_last_kernel_ms.restype = ctypes.c_int
     lib.cmpc_last_kernel_name.argtypes = [vp]

@@ -74,7 +74,10 @@ __device__ __forceinline__ int cmpc_order_bucket(const double *__restrict__ r, i
 // first spare word: consecutive ticks of a closed loop take similar numbers of iterations.  One bucket per iteration
 // there; the formula's buckets (10 + b / 2 iterations) and these meet around 20 iterations, which is where a mixed
 // batch needs them comparable (an instance without a state is a cold solve).
+// consts (cmpc_solve_batch_consts, else null): the instance's own row supplies g and cz_max (a row the solver will refuse
+// lands wherever its numbers put it: the order never changes a result).
 __global__ void __launch_bounds__(256) cmpc_order_score_kernel(int B, int N, double omega, double cz_max, const double *__restrict__ recs,
+                                                               const double *__restrict__ consts,
                                                                const double *__restrict__ state_in, size_t nstate, size_t mu_word,
                                                                int *__restrict__ key, int *__restrict__ counters) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -84,7 +87,14 @@ __global__ void __launch_bounds__(256) cmpc_order_score_kernel(int B, int N, dou
     const double ms = state_in[(size_t)i * nstate + mu_word], cnt = state_in[(size_t)i * nstate + mu_word + 1];
     if (ms > 0.0 && ms < INFINITY && cnt >= 1.0 && cnt < 1e6) b = (cnt < ORDER_BUCKETS - 1) ? (int)cnt : ORDER_BUCKETS - 1;
   }
-  if (b < 0) b = cmpc_order_bucket(recs + (size_t)i * CMPC_NREC(N), N, omega, cz_max);
+  if (b < 0) {
+    if (consts) {
+      const double *row = consts + (size_t)i * CMPC_NCONST;
+      cz_max = row[CMPC_CIDX(cz_max)];
+      omega = sqrt(row[CMPC_CIDX(g)] / cz_max);
+    }
+    b = cmpc_order_bucket(recs + (size_t)i * CMPC_NREC(N), N, omega, cz_max);
+  }
   key[i] = b;
   atomicAdd(counters + 3 + b, 1);
 }
@@ -208,6 +218,71 @@ __global__ void __launch_bounds__(128, WPS) cmpc_solve_pair_gain_kernel(cmpc::KA
     s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr,
             ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr, ka.out + (size_t)p * nsol, ka.status + p,
             ka.iters + p, ka.kkt + p);
+  }
+}
+
+// Per-instance constants (cmpc_solve_batch_consts): the loops above with Solver<..., CONSTS = true>.  consts
+// [B][CMPC_NCONST]: row p belongs to instance p, the wave-uniform index the loop already forms, so the row's address is in
+// scalar registers and its entries are scalar loads.  A row the solver cannot work with (cmpc::consts_row_ok) is answered
+// without a solve.  Kernels of their own, so that the plain ones are left as they are.
+template <int NV, int NW>
+__global__ void __launch_bounds__(64 * NW, (NV == 4 ? CMPC_WAVES_PER_SIMD : 1)) cmpc_solve_consts_kernel(cmpc::KArgs ka, const double *__restrict__ consts,
+                                                                                                          int *ticket, const int *__restrict__ order) {
+  using D = cmpc::Dims<NV, NW>;
+  __shared__ __attribute__((aligned(16))) double lds[D::LDS_DOUBLES];
+  __shared__ int next;
+  double *slab = ka.scratch + (size_t)blockIdx.x * ka.scratch_stride;
+  const size_t nrec = CMPC_NREC(ka.sp.N), nsol = CMPC_NSOL(ka.sp.N, NV), nstate = CMPC_NSTATE(ka.sp.N, NV);
+  for (;;) {
+    const int tid = (NW == 1) ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : (int)threadIdx.x;
+    if (tid == 0) next = atomicAdd(ticket, 1);
+    __syncthreads();
+    // (the ticket is wave-uniform and said so before the exit test: a loop whose exit the compiler takes for divergent turns
+    // every per-instance address that crosses the refusal branch -- record, row, outputs -- into a vector register)
+    const int tk = __builtin_amdgcn_readfirstlane(next);
+    __syncthreads();
+    if (tk >= ka.B) break;
+    const int p = __builtin_amdgcn_readfirstlane(order[tk]);
+    cmpc::Solver<NV, NW, false, false, true> s(ka, lds, slab, ka.recs + (size_t)p * nrec);
+    s.crow = CMPC_CROW(consts + (size_t)p * CMPC_NCONST);
+    double *so = ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr;
+    // (the verdict on the row is the same in every lane; said so, the refusal is a uniform branch and the per-instance
+    // addresses -- record, row, outputs -- stay in scalar registers across it)
+    if (CMPC_UNIFORM_INT((int)cmpc::consts_row_ok(s.crow)))
+      s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr, so,
+              ka.out + (size_t)p * nsol, ka.status + p, ka.iters + p, ka.kkt + p);
+    else
+      s.reject(so, ka.out + (size_t)p * nsol, ka.status + p, ka.iters + p, ka.kkt + p);
+  }
+}
+
+template <int NV, int WPS>
+__global__ void __launch_bounds__(128, WPS) cmpc_solve_pair_consts_kernel(cmpc::KArgs ka, const double *__restrict__ consts, int *ticket,
+                                                                          const int *__restrict__ order) {
+  using D = cmpc::Dims<NV, 1, true>;
+  __shared__ __attribute__((aligned(16))) double lds[2 * D::LDS_DOUBLES];
+  __shared__ int next;
+  double *slab = ka.scratch + (size_t)blockIdx.x * ka.scratch_stride;
+  const size_t nrec = CMPC_NREC(ka.sp.N), nsol = CMPC_NSOL(ka.sp.N, NV), nstate = CMPC_NSTATE(ka.sp.N, NV);
+  for (;;) {
+    if (threadIdx.x == 0) next = atomicAdd(ticket, 1);
+    __syncthreads();
+    // (the ticket is wave-uniform and said so before the exit test: a loop whose exit the compiler takes for divergent turns
+    // every per-instance address that crosses the refusal branch -- record, row, outputs -- into a vector register)
+    const int tk = __builtin_amdgcn_readfirstlane(next);
+    __syncthreads();
+    if (tk >= ka.B) break;
+    const int p = __builtin_amdgcn_readfirstlane(order[tk]);
+    cmpc::Solver<NV, 1, true, false, true> s(ka, lds, slab, ka.recs + (size_t)p * nrec);
+    s.crow = CMPC_CROW(consts + (size_t)p * CMPC_NCONST);
+    double *so = ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr;
+    // (the verdict on the row is the same in every lane; said so, the refusal is a uniform branch and the per-instance
+    // addresses -- record, row, outputs -- stay in scalar registers across it)
+    if (CMPC_UNIFORM_INT((int)cmpc::consts_row_ok(s.crow)))
+      s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr, so,
+              ka.out + (size_t)p * nsol, ka.status + p, ka.iters + p, ka.kkt + p);
+    else
+      s.reject(so, ka.out + (size_t)p * nsol, ka.status + p, ka.iters + p, ka.kkt + p);
   }
 }
 
@@ -469,10 +544,11 @@ int cmpc_solve_batch(cmpc_handle *h, int32_t B, const double *params, const doub
 
 }  // extern "C"
 
-// cmpc_solve_batch_state and cmpc_solve_batch_gain: gain == nullptr launches the plain kernels
+// cmpc_solve_batch_state, cmpc_solve_batch_gain and cmpc_solve_batch_consts: gain == nullptr and consts == nullptr launch the
+// plain kernels (never both given: there is no gain variant with per-instance constants)
 static int solve_batch(cmpc_handle *h, int32_t B, const double *params, const double *warm_XU, const double *state_in,
                        double *out_XU, double *state_out, int32_t *status, int32_t *iters, double *kkt_res, double *gain,
-                       void *stream) {
+                       const double *consts, void *stream) {
   if (!h) return fail(nullptr, "cmpc_solve_batch: null handle");
   if (B < 0) return fail(h, "cmpc_solve_batch: negative batch");
   if (B == 0) return 0;
@@ -505,7 +581,7 @@ static int solve_batch(cmpc_handle *h, int32_t B, const double *params, const do
   HIP_TRY(h, hipEventRecord(h->ev0, st));
   const double omega = sqrt(h->spec.g / h->spec.cz_max);                   // natural frequency of the pendulum at the height limit
   const size_t nstate = CMPC_NSTATE(h->spec.N, h->spec.nv), mu_word = nstate - 8 - 2 * (size_t)(h->spec.N + 1);
-  hipLaunchKernelGGL(cmpc_order_score_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, h->spec.N, omega, h->spec.cz_max, params, state_in, nstate,
+  hipLaunchKernelGGL(cmpc_order_score_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, h->spec.N, omega, h->spec.cz_max, params, consts, state_in, nstate,
                      mu_word, h->order + B, h->ticket);
   hipLaunchKernelGGL(cmpc_order_scatter_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, h->order + B, h->order, h->ticket);
   const bool pair = h->spec.nv == 4 && B <= h->pair_max_batch;   // the batch does not fill the GPU for long: two waves per instance
@@ -525,6 +601,21 @@ static int solve_batch(cmpc_handle *h, int32_t B, const double *params, const do
     } else {
       hipLaunchKernelGGL((cmpc_solve_gain_kernel<8, cmpc::WAVES_NV8>), dim3(grid), dim3(64 * cmpc::WAVES_NV8), 0, st, ka, gain, h->gbuf, h->ticket, h->order);
       h->last_kernel = "cmpc_solve_gain_kernel<8, 2>";
+    }
+  } else if (consts) {
+    if (pair) {
+      const dim3 pg(launch_grid);
+#ifdef CMPC_DEV_KNOBS
+      if (h->pair_per_cu < 3) { hipLaunchKernelGGL((cmpc_solve_pair_consts_kernel<4, 1>), pg, dim3(128), 0, st, ka, consts, h->ticket, h->order); h->last_kernel = "cmpc_solve_pair_consts_kernel<4, 1>"; }
+      else
+#endif
+      { hipLaunchKernelGGL((cmpc_solve_pair_consts_kernel<4, 2>), pg, dim3(128), 0, st, ka, consts, h->ticket, h->order); h->last_kernel = "cmpc_solve_pair_consts_kernel<4, 2>"; }
+    } else if (h->spec.nv == 4) {
+      hipLaunchKernelGGL((cmpc_solve_consts_kernel<4, 1>), dim3(grid), dim3(64), 0, st, ka, consts, h->ticket, h->order);
+      h->last_kernel = "cmpc_solve_consts_kernel<4, 1>";
+    } else {
+      hipLaunchKernelGGL((cmpc_solve_consts_kernel<8, cmpc::WAVES_NV8>), dim3(grid), dim3(64 * cmpc::WAVES_NV8), 0, st, ka, consts, h->ticket, h->order);
+      h->last_kernel = "cmpc_solve_consts_kernel<8, 2>";
     }
   } else if (pair) {
     const dim3 pg(launch_grid);
@@ -551,7 +642,20 @@ extern "C" {
 int cmpc_solve_batch_state(cmpc_handle *h, int32_t B, const double *params, const double *warm_XU, const double *state_in,
                            double *out_XU, double *state_out, int32_t *status, int32_t *iters, double *kkt_res,
                            void *stream) {
-  return solve_batch(h, B, params, warm_XU, state_in, out_XU, state_out, status, iters, kkt_res, nullptr, stream);
+  return solve_batch(h, B, params, warm_XU, state_in, out_XU, state_out, status, iters, kkt_res, nullptr, nullptr, stream);
+}
+
+void cmpc_spec_consts(const cmpc_spec *spec, double row[CMPC_NCONST]) {
+  // (the row IS the block of the spec from delta to relax: cmpc_kernel.hpp, CMPC_CIDX)
+  memcpy(row, &spec->delta, CMPC_NCONST * sizeof(double));
+}
+
+int cmpc_solve_batch_consts(cmpc_handle *h, int32_t B, const double *params, const double *consts, const double *warm_XU,
+                            const double *state_in, double *out_XU, double *state_out, int32_t *status, int32_t *iters,
+                            double *kkt_res, void *stream) {
+  if (!h) return fail(nullptr, "cmpc_solve_batch_consts: null handle");
+  if (!consts) return fail(h, "cmpc_solve_batch_consts: null consts (use cmpc_solve_batch_state for the handle's constants)");
+  return solve_batch(h, B, params, warm_XU, state_in, out_XU, state_out, status, iters, kkt_res, nullptr, consts, stream);
 }
 
 int cmpc_solve_batch_gain(cmpc_handle *h, int32_t B, const double *params, const double *warm_XU, const double *state_in,
@@ -564,7 +668,7 @@ int cmpc_solve_batch_gain(cmpc_handle *h, int32_t B, const double *params, const
     if (!guard.ok) return fail(h, "cmpc_solve_batch_gain: cannot select the handle's device");
     HIP_TRY(h, hipMalloc(&h->gbuf, (size_t)h->slabs * CMPC_NSTATE(h->spec.N, h->spec.nv) * sizeof(double)));
   }
-  return solve_batch(h, B, params, warm_XU, state_in, out_XU, state_out, status, iters, kkt_res, gain, stream);
+  return solve_batch(h, B, params, warm_XU, state_in, out_XU, state_out, status, iters, kkt_res, gain, nullptr, stream);
 }
 
 int cmpc_last_kernel_ms(cmpc_handle *h, float *ms) {

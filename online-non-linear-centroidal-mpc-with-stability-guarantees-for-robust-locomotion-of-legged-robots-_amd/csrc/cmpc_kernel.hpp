@@ -68,10 +68,23 @@ typedef double cmpc_v4d __attribute__((ext_vector_type(4)));
 static __device__ __forceinline__ double cmpc_fresh(double a) { asm volatile("" : "+s"(a)); return a; }
 #define CMPC_FRESH_D(x) cmpc_fresh(x)
 #ifdef CMPC_FRESH_SPEC
-#define SPD(field) cmpc_fresh(sp.field)
+#define SPD(field) cmpc_fresh(CMPC_SPEC_OR_ROW(field))
 #else
-#define SPD(field) (sp.field)
+#define SPD(field) CMPC_SPEC_OR_ROW(field)
 #endif
+// The per-instance row of constants (Solver<..., CONSTS = true>, cmpc_solve_batch_consts) is read through the constant
+// address space: a load from it at a wave-uniform address is a scalar load, invariant for the whole kernel, so the
+// compiler may repeat it at every use instead of keeping the value -- exactly what it does with a kernel argument.  (The
+// table is written before the launch and never by the kernel, which is what the address space promises.)
+typedef const double __attribute__((address_space(4))) *cmpc_crow_t;
+#define CMPC_CROW(p) ((cmpc_crow_t)(p))
+// ... and it has to: the row's address is made opaque at every use (it stays in its scalar register pair), so that neither
+// the load nor what the optimiser derives from a loaded constant (2 w, d k1 / m, ...) is hoisted to the top of the solve
+// and carried in VECTOR registers through it.  Measured on the cross-compiled ISA: 32 / 24 bytes of scratch per lane in the
+// one-wave / pair kernel without this (39 scalar loads), none with it (one load per use).  The constraint needs the
+// address in scalar registers, i.e. wave-uniform as the compiler sees it: the kernels' instance loops take care of that.
+static __device__ __forceinline__ cmpc_crow_t cmpc_fresh_row(cmpc_crow_t r) { asm volatile("" : "+s"(r)); return r; }
+#define CMPC_ROW_AT(r, i) (cmpc_fresh_row(r)[i])
 // a double every lane holds the same value of, said so: it lives in a scalar register pair (spilled, that is two
 // v_readlane; a vector register spilled is a scratch load whose wait also drains every global load in flight)
 static __device__ __forceinline__ double cmpc_uniform_d(double v) {
@@ -107,10 +120,19 @@ static __device__ __forceinline__ double cmpc_uniform_d(double v) {
 #endif
 #ifndef CMPC_RELANE
 #define CMPC_RELANE(x) do { } while (0)
-#define SPD(field) (sp.field)
+#define SPD(field) CMPC_SPEC_OR_ROW(field)
+typedef const double *cmpc_crow_t;
+#define CMPC_CROW(p) ((cmpc_crow_t)(p))
+#define CMPC_ROW_AT(r, i) ((r)[i])
 #define CMPC_FRESH_D(x) (x)
 #define CMPC_UNIFORM_D(x) (x)
 #endif
+// A constant of the problem where the solver uses it: the handle's spec (a kernel argument), or -- CONSTS variants -- the
+// instance's own row of CMPC_NCONST doubles, which has the field order of cmpc_spec from `delta` on (include/cmpc.h).
+#define CMPC_CIDX(field) ((int)((__builtin_offsetof(cmpc_spec, field) - __builtin_offsetof(cmpc_spec, delta)) / sizeof(double)))
+#define CMPC_SPEC_OR_ROW(field) (CONSTS ? CMPC_ROW_AT(crow, CMPC_CIDX(field)) : sp.field)
+static_assert(CMPC_CIDX(relax) == CMPC_NCONST - 1 && CMPC_CIDX(box[2]) == 13 && __builtin_offsetof(cmpc_spec, tol) == __builtin_offsetof(cmpc_spec, relax) + sizeof(double),
+              "the row of per-instance constants is the block of cmpc_spec from delta to relax");
 // x * y + z in ONE rounding, spelled out.  Everywhere else the multiply-adds are formed by the compiler's contraction of
 // a * b + c, whose choices depend on the code around (which product is hoisted out of a masked block, which sum is
 // restarted at a neighbouring add): fine for code both solver kernels share verbatim, not for G'PG, which the single wave
@@ -419,6 +441,21 @@ struct GArr {
   CMPC_DEV cmpc_v2d &pair(unsigned i) const { return *(cmpc_v2d *)((char *)p + (size_t)(i * 16u)); }   // 16-byte aligned pairs
 };
 
+// A row of per-instance constants (CONSTS variants; layout: include/cmpc.h) the solver can work with: every entry finite,
+// the lengths (delta, g, cz_max, the contact box, the foot) positive, the weights, prox and relax not negative (k1, k2: any
+// finite value).  Checked by the wave that draws the instance, on scalar loads; an instance whose row fails is not solved
+// (Solver::reject).
+CMPC_DEV bool consts_row_ok(cmpc_crow_t row) {
+  bool ok = true;
+  for (int i = 0; i < CMPC_NCONST; ++i) {
+    const double v = row[i];
+    const bool positive = i == CMPC_CIDX(delta) || i == CMPC_CIDX(g) || (i >= CMPC_CIDX(cz_max) && i <= CMPC_CIDX(foot_width));
+    const bool gain = i == CMPC_CIDX(k1) || i == CMPC_CIDX(k2);       // (any finite value)
+    ok = ok && v < INFINITY && v > -INFINITY && (positive ? v > 0.0 : (gain || v >= 0.0));   // (a NaN fails every comparison)
+  }
+  return ok;
+}
+
 // PIPE (one-wave solver only): the workgroup is a PAIR of waves on one instance.  Wave 1 evaluates stage k - 1 (loads,
 // geometry, inequality rows, Hessian rows, gradient: everything that does not need the cost-to-go of stage k) into one of
 // two LDS images while wave 0 runs the Riccati step of stage k (G'PG, factorisation, backward vectors, factor store) out
@@ -428,7 +465,11 @@ struct GArr {
 // GAIN: the variant behind cmpc_solve_batch_gain (include/cmpc.h).  It solves exactly as the plain solver does (every
 // line it adds is behind `if constexpr (GAIN)`) and then forms the first-stage gain d(x_1, u_0)/dx0 at the returned point
 // (Solver::gain_tail).
-template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false> struct Solver {
+// CONSTS: the variant behind cmpc_solve_batch_consts.  The eighteen constants of cmpc_spec from `delta` to `relax` come
+// from the instance's own row (`crow`, CMPC_NCONST doubles) instead of the handle's spec; N, nv, max_iter, tol and acc_tol
+// stay the handle's.  The instance index is wave-uniform, so a row entry is a scalar load into scalar registers, as a
+// kernel argument is -- nothing else in the solver changes (SPD()).
+template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS = false> struct Solver {
   using D = Dims<NV, NW, PIPE>;
   // PIPE: words behind the two LDS images.  [0..5] error measures, [6] ap, [7] ad, [8..9] factorisation verdict of the
   // sweep step in hand (by step parity), [16 ..): du_k of the forward sweep by stage parity (read by the slack wave)
@@ -467,6 +508,7 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false> struct Solve
   double *gain_out = nullptr;
   GArr gbuf{nullptr};
   bool gain_sweep = false;   // the sweep of gain_tail: row weights capped (GAIN_SIG_CAP, GAIN_SIG_CAP_BOX)
+  cmpc_crow_t crow = nullptr;   // CONSTS only: this instance's row of constants (read only, never written by the kernel)
 
   CMPC_DEV Solver(const KArgs &a, double *l, double *g, const double *r)
       : ka(a), sp(a.sp), lds(l), ldsR(l), gs{g}, rec{const_cast<double *>(r)}, N(a.sp.N), lane(CMPC_LANE) {
@@ -2577,6 +2619,22 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false> struct Solve
     }
     if (wv == 0) gain_step(good);
     if constexpr (PIPE) pair_sync(); else gsync();
+  }
+
+  // CONSTS: the verdict of an instance whose row of constants is not usable (consts_row_ok): no solve, CMPC_NUMERICAL, a
+  // solution record of NaN, no solver state -- what the caller of a NaN record finds, without running into the row's values.
+  CMPC_DEV void reject(double *state_out, double *out_, int32_t *status, int32_t *iters, double *kkt_out) {
+    if (!PIPE || wv == 0) {
+      const GArr out{out_};
+      const double nanv = __builtin_nan("");
+      for (int e = lane; e < (N + 1) * CMPC_NX + N * NU; e += WS) out[e] = nanv;
+      if (lane == 0) {
+        *status = CMPC_NUMERICAL; *iters = 0; *kkt_out = INFINITY;
+        if (state_out) { GArr{state_out}[D::state_mu(N)] = 0.0; GArr{state_out}[D::state_mu(N) + 1] = 0.0; }
+      }
+    }
+    // (ends as solve() does: the lanes are together again before the caller's loop draws the next instance)
+    if constexpr (PIPE) pair_sync(); else sync();
   }
 
   // ---------------------------------------------------------------------------------------

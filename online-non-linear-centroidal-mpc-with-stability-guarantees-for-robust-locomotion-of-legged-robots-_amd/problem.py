@@ -24,6 +24,13 @@ import ctypes
 import numpy as np
 
 NX = 20
+#: one row of per-instance constants (``cmpc_solve_batch_consts``, CMPC_NCONST doubles): the fields of ``cmpc_spec`` from
+#: ``delta`` to ``relax``, ``box`` as three entries
+CONST_FIELDS = ("delta", "g", "k1", "k2", "w_rate", "w_hw", "w_cxy", "w_cz_const", "w_foot", "w_force", "cz_max",
+                "box[0]", "box[1]", "box[2]", "foot_length", "foot_width", "prox", "relax")
+NCONST = len(CONST_FIELDS)
+#: what a batch with per-instance constants still shares (the handle's)
+SHARED_FIELDS = ("N", "nv", "max_iter", "tol", "acc_tol")
 
 
 @dataclass
@@ -78,6 +85,15 @@ class ProblemSpec:
             return np.array(corners + [[L, 0., 0.], [0., -W, 0.], [-L, 0., 0.], [0., W, 0.]])
         raise ValueError("nv must be 4 or 8")
 
+    def consts_row(self):
+        """The (18,) float64 row of ``CONST_FIELDS`` that reproduces this spec in ``solve_with_consts``."""
+        box = tuple(self.box)
+        if len(box) != 3:
+            raise ValueError("box must have three entries")
+        return np.array([self.delta, self.g, self.k1, self.k2, self.w_rate, self.w_hw, self.w_cxy, self.w_cz_const,
+                         self.w_foot, self.w_force, self.cz_max, box[0], box[1], box[2], self.foot_length,
+                         self.foot_width, self.prox, self.relax], dtype=np.float64)
+
     @classmethod
     def from_params(cls, params, payload=False, **kw):
         """Constants as ``centroidal_mpc.__init__`` derives them from the params dict."""
@@ -88,6 +104,19 @@ class ProblemSpec:
             k1, k2 = (5.0, 0.2) if rate == 10 else (4.0, 0.1)
         return cls(N=params['N'], delta=params['world_time_step'] * rate, g=params['g'],
                    k1=k1, k2=k2, w_rate=0.0 if rate == 10 else 1.0, **kw)
+
+
+def consts_rows(specs):
+    """(B, 18) float64 rows for a sequence of specs that will share one launch.  The specs must agree on what the launch
+    shares (``SHARED_FIELDS``: the horizon, the vertex count, the iteration cap and the two tolerances stay the handle's)."""
+    specs = list(specs)
+    for f in SHARED_FIELDS:
+        vals = {getattr(s, f) for s in specs}
+        if len(vals) > 1:
+            raise ValueError(f"specs of one batch must share {f}: got {sorted(vals)}")
+    if not specs:
+        return np.zeros((0, NCONST))
+    return np.stack([s.consts_row() for s in specs])
 
 
 def contact_flags(planner, t, N, rate=1):

@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import capi
-from .problem import NX, ProblemSpec, to_cspec
+from .problem import NCONST, NX, ProblemSpec, to_cspec
 
 # per-instance outcome (include/cmpc.h): 3 = stopped short of `tol` with a KKT error within `acc_tol`
 # (IPOPT's "Solved To Acceptable Level", which CasADi's Opti.solve() returns without raising)
@@ -71,7 +71,19 @@ class BatchedCentroidalMPC:
         """
         return self._solve(records, warm, out, state, state_out, None)
 
-    def _solve(self, records, warm, out, state, state_out, gain):
+    def solve_with_consts(self, records, consts, warm=None, out=None, state=None, state_out=None):
+        """``solve`` with per-instance constants: ``consts`` (B, 18) fp64 on this GPU, one row per instance in the order
+        of ``problem.CONST_FIELDS`` (``ProblemSpec.consts_row()``, ``problem.consts_rows(specs)``).  Instance b is solved
+        with this handle's spec in which those eighteen fields are replaced by ``consts[b]``; N, nv, max_iter, tol,
+        acc_tol and the kernel choice stay the handle's.  Rows that reproduce the handle's spec give bit for bit what
+        ``solve`` gives.  A row the solver cannot use (non-finite; a length, g or delta <= 0; a negative weight, prox or
+        relax) makes that instance -- and no other -- return status 2 with a NaN solution: checked on the GPU, no
+        synchronisation (``cmpc_solve_batch_consts``, include/cmpc.h)."""
+        if not isinstance(consts, torch.Tensor):
+            raise ValueError(f"consts must be a contiguous fp64 CUDA tensor of shape (B, {NCONST})")
+        return self._solve(records, warm, out, state, state_out, None, consts)
+
+    def _solve(self, records, warm, out, state, state_out, gain, consts=None):
         sp = self.spec
         if not (records.is_cuda and records.dtype == torch.float64 and records.is_contiguous()):
             raise ValueError("records must be a contiguous fp64 CUDA tensor")
@@ -84,6 +96,10 @@ class BatchedCentroidalMPC:
             if not (warm.is_cuda and warm.dtype == torch.float64 and warm.is_contiguous()
                     and tuple(warm.shape) == (B, sp.nsol) and warm.device == self.device):
                 raise ValueError(f"warm must be a contiguous fp64 CUDA tensor of shape (B, {sp.nsol})")
+        if consts is not None:
+            if not (consts.is_cuda and consts.dtype == torch.float64 and consts.is_contiguous()
+                    and tuple(consts.shape) == (B, NCONST) and consts.device == self.device):
+                raise ValueError(f"consts must be a contiguous fp64 CUDA tensor of shape (B, {NCONST}) on {self.device}")
         for name, t in (("state", state), ("state_out", state_out)):
             if t is not None and not (t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
                                       and tuple(t.shape) == (B, sp.nstate) and t.device == self.device):
@@ -104,7 +120,9 @@ class BatchedCentroidalMPC:
                 state.data_ptr() if state is not None else None, out.data_ptr(),
                 state_out.data_ptr() if state_out is not None else None,
                 status.data_ptr(), iters.data_ptr(), kkt.data_ptr())
-        if gain is None:
+        if consts is not None:
+            rc = self._lib.cmpc_solve_batch_consts(*args[:3], consts.data_ptr(), *args[3:], ctypes.c_void_p(stream))
+        elif gain is None:
             rc = self._lib.cmpc_solve_batch_state(*args, ctypes.c_void_p(stream))
         else:
             rc = self._lib.cmpc_solve_batch_gain(*args, gain.data_ptr(), ctypes.c_void_p(stream))
