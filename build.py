@@ -98,6 +98,34 @@ def build_emu_consts(force=False):
     return out
 
 
+def build_emu_reuse(force=False, reuse=True):
+    """Host emulation with counters on the retried factorisations (tests/emu/cmpc_emu_reuse.cpp): test harness only.
+    reuse=False builds the kernel source with -DCMPC_NO_EVAL_REUSE, the path that evaluates every stage of a retry pass again."""
+    src = os.path.join(ROOT, "tests", "emu", "cmpc_emu_reuse.cpp")
+    out = os.path.join(ROOT, "tests", "emu", "libcmpc_emu_reuse.so" if reuse else "libcmpc_emu_noreuse.so")
+    deps = [src, os.path.join(ROOT, "tests", "emu", "cmpc_emu.cpp"), os.path.join(PKG, "csrc", "cmpc_kernel.hpp"),
+            os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp"),
+            os.path.join(ROOT, "include", "cmpc.h")]
+    if force or _newer(out, deps):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-fPIC", "-shared", "-pthread"]
+                              + ([] if reuse else ["-DCMPC_NO_EVAL_REUSE"]) + ["-o", out, src])
+    return out
+
+
+def build_hip_no_reuse(force=False, profile=False):
+    """Diagnostic variant (tools/ only; loaded through CMPC_LIB_PATH): -DCMPC_NO_EVAL_REUSE, the one-wave 4-vertex kernel that
+    evaluates every stage of a retry pass again -- the third leg of the A/B runs, and with profile=True the `before` of
+    tools/phase_profile.py's retry figures."""
+    src = os.path.join(PKG, "csrc", "cmpc_hip.hip")
+    deps = [src, os.path.join(PKG, "csrc", "cmpc_kernel.hpp"), os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp"),
+            os.path.join(ROOT, "include", "cmpc.h")]
+    out = os.path.join(ROOT, "tools", "libcmpc_amd_noreuse_prof.so" if profile else "libcmpc_amd_noreuse.so")
+    if force or _newer(out, deps):
+        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DCMPC_NO_EVAL_REUSE"]
+                              + (["-DCMPC_PROFILE"] if profile else []) + ["-o", out, src, os.path.join(PKG, "csrc", "wbc_qp.hip")])
+    return out
+
+
 def build_device_unit(force=False):
     """GPU-tier unit harness for the device-only primitives (tests/gpu_unit): never loaded by the package."""
     src = os.path.join(ROOT, "tests", "gpu_unit", "cmpc_device_unit.hip")
@@ -132,5 +160,7 @@ if __name__ == "__main__":
     print(build_emu(force))
     print(build_emu_gain(force))
     print(build_emu_consts(force))
+    print(build_emu_reuse(force))
+    print(build_emu_reuse(force, reuse=False))
     print(build_device_unit(force))
     print(build_tools(force))

@@ -512,7 +512,7 @@ int cmpc_create(const cmpc_spec *spec, int device, cmpc_handle **out) {
 #endif
   h->slab_doubles = slab_doubles(spec);
 #ifdef CMPC_PROFILE
-  if (hipMalloc(&h->prof, 28 * sizeof(long long)) == hipSuccess) (void)hipMemset(h->prof, 0, 28 * sizeof(long long));
+  if (hipMalloc(&h->prof, CMPC_NPROF * sizeof(long long)) == hipSuccess) (void)hipMemset(h->prof, 0, CMPC_NPROF * sizeof(long long));
 #endif
   if (hipMalloc(&h->scratch, (size_t)h->slabs * h->slab_doubles * sizeof(double)) != hipSuccess ||
       hipMalloc(&h->ticket, ORDER_COUNTERS * sizeof(int)) != hipSuccess || hipEventCreate(&h->ev0) != hipSuccess ||
@@ -770,8 +770,8 @@ int cmpc_debug_slab(cmpc_handle *h, double **ptr, size_t *doubles) {
 /* diagnostic build only: read and reset the phase cycle sums */
 int cmpc_profile_read(cmpc_handle *h, long long *out8) {
   if (!h || !h->prof) return 1;
-  if (hipMemcpy(out8, h->prof, 28 * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return 1;
-  (void)hipMemset(h->prof, 0, 28 * sizeof(long long));
+  if (hipMemcpy(out8, h->prof, CMPC_NPROF * sizeof(long long), hipMemcpyDeviceToHost) != hipSuccess) return 1;
+  (void)hipMemset(h->prof, 0, CMPC_NPROF * sizeof(long long));
   return 0;
 }
 #endif

@@ -60,6 +60,10 @@ typedef double cmpc_v4d __attribute__((ext_vector_type(4)));
 // across the whole solve and spilled)
 #define CMPC_OPAQUE(x) asm volatile("" : "+v"(x))
 #define CMPC_OPAQUE_D(x) asm volatile("" : "+v"(x))
+// a wave-uniform integer, opaque: what is derived from it is formed where it is used, from this one scalar register (left
+// to itself the optimiser keeps every multiple-plus-offset of a stage index as an induction variable of the stage loop,
+// a scalar register each, live across the whole loop -- and spilled)
+#define CMPC_OPAQUE_S(x) asm volatile("" : "+s"(x))
 // a wave-uniform integer the compiler cannot prove uniform: said so, it lives in a scalar register
 #define CMPC_UNIFORM_INT(x) __builtin_amdgcn_readfirstlane(x)
 // a wave-uniform number of the problem spec (a kernel argument, in scalar registers), opaque at every use: what the
@@ -67,10 +71,14 @@ typedef double cmpc_v4d __attribute__((ext_vector_type(4)));
 // and keeps in VECTOR registers through the whole solve (there is no scalar fp64 arithmetic), forty-five of them
 static __device__ __forceinline__ double cmpc_fresh(double a) { asm volatile("" : "+s"(a)); return a; }
 #define CMPC_FRESH_D(x) cmpc_fresh(x)
+// (SPD() names Solver::EVAL_REUSE: it is for use inside Solver's member functions only, where all its uses are.)
+// (the kernels with the reuse path of the retried factorisation read it so -- Solver::EVAL_REUSE, and see DESIGN.md: with the
+// second path through a stage the spec's words, loaded at kernel entry, no longer fit the scalar registers and their
+// spill lanes took a third vector register, which the vector side does not have)
 #ifdef CMPC_FRESH_SPEC
 #define SPD(field) cmpc_fresh(CMPC_SPEC_OR_ROW(field))
 #else
-#define SPD(field) CMPC_SPEC_OR_ROW(field)
+#define SPD(field) (EVAL_REUSE ? cmpc_fresh(CMPC_SPEC_OR_ROW(field)) : CMPC_SPEC_OR_ROW(field))
 #endif
 // The per-instance row of constants (Solver<..., CONSTS = true>, cmpc_solve_batch_consts) is read through the constant
 // address space: a load from it at a wave-uniform address is a scalar load, invariant for the whole kernel, so the
@@ -145,16 +153,43 @@ static_assert(CMPC_CIDX(relax) == CMPC_NCONST - 1 && CMPC_CIDX(box[2]) == 13 && 
 #ifndef CMPC_UNIFORM_INT
 #define CMPC_UNIFORM_INT(x) (x)
 #endif
+#ifndef CMPC_OPAQUE_S
+#define CMPC_OPAQUE_S(x) do { } while (0)
+#endif
 
 // Optional phase timers (diagnostic build only, -DCMPC_PROFILE): cycles per phase summed over the
 // launch, written to a buffer nothing else reads.
 #if defined(CMPC_PROFILE) && !defined(CMPC_HOST_EMU)
-#define CMPC_TICK(slot) do { long long now_ = clock64(); tprof[slot] += now_ - tlast; tlast = now_; } while (0)
+// (slots 28 ..: the retried factorisations.  28 retry passes, 29 stages the failed passes had evaluated, 30 stages a retry
+// pass took from the slab; ticks of a retry pass inside the stages a failed pass of the iteration had evaluated: 31 the
+// phases that do not depend on the regularisation -- geometry, inequality rows, gradient / residual, their slab stores --,
+// 32 stage loads and barrier weights, 33 everything else of those stages, 34 the reloads of the reuse path; 35 retry passes
+// that failed again)
+// (phase slot -> retry slot; the same table, by name, in tools/phase_profile.py)
+static __device__ __forceinline__ constexpr int cmpc_retry_class(int slot) {
+  return (slot == 11 || slot == 12 || slot == 26 || slot == 0) ? 31      // geometry, inequality rows, gradient / residual, evaluation stores
+       : (slot == 24 || slot == 25) ? 32                                  // stage loads, barrier weights
+       : (slot == 27) ? 34                                                // reloads of the reuse path
+       : 33;                                                              // everything a retry has to redo
+}
+#define CMPC_TICK(slot) do { long long now_ = clock64(); tprof[slot] += now_ - tlast; \
+    if (prof_retry) tprof[cmpc_retry_class(slot)] += now_ - tlast; \
+    tlast = now_; } while (0)
 #define CMPC_TICK_RESET() do { tlast = clock64(); } while (0)
+#define CMPC_RETRY_STAT(slot, n) do { tprof[slot] += (n); } while (0)
+#define CMPC_RETRY_MARK(on) do { prof_retry = (on); } while (0)
+#define CMPC_RETRY_TRACK 1
 #else
 #define CMPC_TICK(slot) do { } while (0)
 #define CMPC_TICK_RESET() do { } while (0)
+#define CMPC_RETRY_MARK(on) do { } while (0)
+#define CMPC_RETRY_TRACK 0
 #endif
+// retry counters of the test harness (tests/emu/cmpc_emu_reuse.cpp); the profile build's are phase-timer slots
+#ifndef CMPC_RETRY_STAT
+#define CMPC_RETRY_STAT(slot, n) do { } while (0)
+#endif
+#define CMPC_NPROF 36
 
 namespace cmpc {
 
@@ -171,7 +206,7 @@ struct KArgs {
   double *kkt;
   double *scratch;      // [grid][scratch_stride]
   size_t scratch_stride;
-  long long *prof;      // [8] phase cycle sums (CMPC_PROFILE builds), else null
+  long long *prof;      // [CMPC_NPROF] phase cycle sums (CMPC_PROFILE builds), else null
   // levels of the outer loop derived from sp.tol (cmpc::fill_levels, on the host): as kernel arguments they sit in scalar
   // registers; computed in the kernel they are vector-ALU results hoisted to kernel entry -- and spilled
   double tol_acc, tol_tenth;
@@ -408,6 +443,12 @@ template <int NV, int NW = 1, bool PIPE = false> struct Dims : LdsMap<NV, NW, PI
   static constexpr int gL1 = gG + NI;         // l = gL + mu*gL1,  p = gPV + mu*gPV1
   static constexpr int gPV1 = gL1 + NU;
   static constexpr int STAGE = ((gPV1 + NXA + 7) / 8) * 8;
+  // What a retried factorisation takes back from the failed pass instead of evaluating the stage again (one-wave 4-vertex
+  // solver, Solver::EVAL_REUSE), beside gGH, gB and gAL above: the gradient parts h0 / h1 before the column lists' products
+  // are added, the barrier weights sigma = z / s, R'v_j, the two yaw curvatures and pi.  An array of its own behind the iterate
+  // arrays (the stage blocks keep their layout), one block per stage.
+  static constexpr int rH0 = 0, rH1 = rH0 + NZ, rW0 = rH1 + NZ, rVDV = rW0 + NI, rQ = rVDV + 3 * NF, rPI = rQ + 2;
+  static constexpr int RE_STAGE = COMPACT ? ((rPI + 3 + 7) / 8) * 8 : 0;
   // solver state of one instance (CMPC_NSTATE): [XU | lam (N+1) x NXA | s (N+1) x NI | z (N+1) x NI | mu, 7 spare |
   // contact flags of the N+1 nodes, left then right]
   static constexpr int state_lam(int N) { return CMPC_NSOL(N, NV); }
@@ -422,6 +463,7 @@ template <int NV, int NW = 1, bool PIPE = false> struct Dims : LdsMap<NV, NW, PI
     n += (size_t)(N + 1) * NXA * 4;   // x, lam, dx, lamn
     n += (size_t)(N + 1) * NU * 3;    // u, du, uprox
     n += (size_t)(N + 1) * NI * 4;    // s, z, ds, dz
+    n += (size_t)(N + 1) * RE_STAGE;  // evaluation words kept for a retried factorisation
     return (n + 7) / 8 * 8;
   }
 };
@@ -485,6 +527,20 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
                 "pair_vectors reads BV / writes XN1 of the image the Riccati wave is working in");
   static constexpr int NF = D::NF, NU = D::NU, NXA = D::NXA, NZ = D::NZ, NI = D::NI, NH = D::NH, WS = D::WS;
   static_assert(NW == 1 || NU <= 64, "the input rows (pivot chains, substitutions) live in the first wave");
+  // A retry pass of the matrix sweep (larger regularisation, same iterate) takes the stages a failed pass of the iteration
+  // has evaluated from the slab: see eval_stage.  -DCMPC_NO_EVAL_REUSE builds the kernel that evaluates them again.
+#ifdef CMPC_NO_EVAL_REUSE
+  static constexpr bool EVAL_REUSE = false;
+#else
+  static constexpr bool EVAL_REUSE = NV == 4 && NW == 1 && !PIPE && !GAIN && D::GT_FIRST;
+#endif
+  static constexpr bool RETRY_TRACK_POSSIBLE = NV == 4 && NW == 1 && !PIPE && !GAIN;
+  // where a failed pass leaves its error measures for the retry (six words per lane in the M region, dead from the failed
+  // factorisation to the terminal node's zero fill; behind the geometry's overlays GH, BV, r_j): in registers they were live
+  // across the retry loop -- and spilled
+  static constexpr int ER_AT = 256;
+  static_assert(!RETRY_TRACK_POSSIBLE || (ER_AT >= 3 * NZ + NXA + 3 * NF && ER_AT + 6 * WS <= D::NTRI), "the parked error measures fit the M region");
+  static constexpr bool RETRY_TRACK = EVAL_REUSE || (CMPC_RETRY_TRACK && NV == 4 && NW == 1 && !PIPE && !GAIN);
 
   const KArgs &ka;
   const cmpc_spec &sp;
@@ -502,7 +558,8 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
   double lg[NH][6];
   double piv_min = PIV_MIN;  // pivot acceptance threshold of the current sweep
   GArr st_in{nullptr};       // solver state resumed from (null: cold rule for slacks / multipliers)
-  long long tprof[28] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
+  long long tprof[CMPC_NPROF] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, tlast = 0;
+  bool prof_retry = false;
   // GAIN only: this instance's gain ([CMPC_NX + NU][CMPC_NX], row-major) and the slot's copy of the saved iterate
   // (CMPC_NSTATE layout; written wherever the solver saves a point to `out`)
   double *gain_out = nullptr;
@@ -532,6 +589,12 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
     gdz = GArr{p};
   }
   CMPC_DEV GArr stage(int k) const { return GArr{gs.p + (size_t)k * D::STAGE}; }
+  // stage k's block of the words kept for a retried factorisation (Dims::rH0 ...), behind the last iterate array
+  // (as a word index into the stage block of node k: the slab's base pointer is the only address kept)
+  CMPC_DEV unsigned restage(int k) const {
+    CMPC_OPAQUE_S(k);
+    return (unsigned)((N + 1 - k) * D::STAGE + (N + 1) * (4 * NXA + 3 * NU + 4 * NI) + k * D::RE_STAGE);
+  }
   CMPC_DEV double &L(int o) const { return lds[o]; }
   CMPC_DEV double &R(int o) const { return ldsR[o]; }         // Riccati-owned words: P, PC, PC1, COLD
   CMPC_DEV void image(int k) { if constexpr (PIPE) lds = ldsR + (k & 1) * D::LDS_DOUBLES; }
@@ -1691,12 +1754,54 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
     return a;
   }
 
-  CMPC_DEV void eval_stage(int k, double mu, double reg, double wz, double x0n2, Err &er, bool init) {
+  // reuse (EVAL_REUSE, wave-uniform): a failed pass of this iteration has evaluated the stage at this iterate and barrier
+  // value.  Nothing of the geometry, the inequality rows, the barrier weights or the gradient depends on the
+  // regularisation: the dense rows, b and the Lyapunov gradient come back from the stage block, the raw gradient parts,
+  // sigma, R'v_j and the yaw curvatures from the stage's reuse words (Dims::rH0 ...), every word read by the lane that
+  // stored it; the stage's share of the error measures is in `er` already.  What P_{k+1} or the regularisation enters
+  // (column lists' products, P b, G'PG, the Hessian rows) runs as on a first pass.
+  CMPC_DEV void eval_stage(int k, double mu, double reg, double wz, double x0n2, Err &er, bool init, bool reuse_ = false) {
+    const bool reuse = EVAL_REUSE && reuse_;
     CMPC_RELANE(lane); CMPC_OPAQUE(lane);
+    // (the stage index opaque: the scalar registers the reuse path needs are those the stage loop's induction variables --
+    // k times every array's stride -- held across the whole loop; formed from k where they are used, they cost a multiply)
+    if constexpr (EVAL_REUSE) { CMPC_OPAQUE_S(k); }
+    double re_h0 = 0.0, re_h1 = 0.0, re_al = 0.0, re_w0 = 0.0;
+    if (reuse) {
+      const GArr sk = stage(k); const unsigned re = restage(k);
+      const int cz = (lane < NZ) ? lane : 0, ci = (lane < NI) ? lane : 0;
+      re_al = sk[D::gAL + cz]; re_w0 = sk[re + D::rW0 + ci]; re_h0 = sk[re + D::rH0 + cz]; re_h1 = sk[re + D::rH1 + cz];
+    }
     load_stage(k);
     CMPC_TICK(24);
     const GArr st = stage(k);
-    if (k < N) {
+    if (reuse) {
+      // (One batch of reloads behind the stage's own loads -- issued ahead of them, these words and the stage's fourteen were
+      // more than the register file holds across the LDS commit.  None of them stays in a register: the raw gradient parts
+      // wait in H0 / H1, where the lists' products are added to them, and the two vectors whose LDS home is the P region --
+      // alive until G'PG has consumed P_{k+1} -- in stage vectors this path does not read, the inputs and lam_k for the
+      // Lyapunov gradient, the slacks for sigma.)
+      const unsigned re = restage(k);
+      const int cz = (lane < NZ) ? lane : 0, cx = (lane < NXA) ? lane : 0, ci = (lane < NI) ? lane : 0;
+      static_assert(!EVAL_REUSE || (NH == 1 && NI <= WS && 3 * NF + 5 <= WS && D::rQ == D::rVDV + 3 * NF && D::rPI == D::rQ + 2), "one word of each kept vector per lane");
+      const double re_gh0 = st[D::gGH + cz], re_gh1 = st[D::gGH + D::GHS + cz], re_gh2 = st[D::gGH + 2 * D::GHS + cz];
+      const double re_bv = st[D::gB + cx];      // (the terminal node has no b: its words are never written, and not used below)
+      const double re_vdv = st[re + D::rVDV + ((lane < 3 * NF + 5) ? lane : 0)];      // (R'v_j, then the two yaw curvatures, then pi)
+      // (every lane stores every word, the lanes past a vector's end to the dump slots: selected addresses, no execution
+      // masks -- each mask is a scalar register pair, and the stage loop has none to spare)
+      const int dump = D::oDUMP + (lane & (D::DUMPN - 1));
+      const bool in_z = lane < NZ;
+      L(in_z ? D::oGH + lane : dump) = re_gh0; L(in_z ? D::oGH + NZ + lane : dump) = re_gh1; L(in_z ? D::oGH + 2 * NZ + lane : dump) = re_gh2;
+      L((lane < NXA) ? D::oBV + lane : dump) = (k < N) ? re_bv : 0.0;
+      L((lane < 3 * NF) ? D::oVDV + lane : (lane < 3 * NF + 2) ? D::oMISC + 30 - 3 * NF + lane
+        : (lane < 3 * NF + 5) ? D::oMISC + 9 - (3 * NF + 2) + lane : dump) = re_vdv;
+      static_assert(!EVAL_REUSE || (D::oLAMK == D::oUK + NU && NU + NXA == NZ), "the Lyapunov gradient fits the inputs and lam_k");
+      L(in_z ? D::oUK + lane : dump) = re_al; L(in_z ? D::oH0 + lane : dump) = re_h0; L(in_z ? D::oH1 + lane : dump) = re_h1;
+      L((lane < NI) ? D::oSK + lane : dump) = re_w0;
+      sync();
+      CMPC_RETRY_STAT(30, 1);
+      CMPC_TICK(27);
+    } else if (k < N) {
       stage_geometry(k);
     } else {
       for (int c = lane; c < 3 * NZ; c += WS) L(D::oGH + c) = 0.0;
@@ -1711,6 +1816,8 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
       // rest of the stage needs of the column lists is formed now, while they are in registers: [B A]' applied to
       // lam_{k+1} (dual residual), to p0_{k+1} + P b and to p1_{k+1} (backward vectors; parked in H0 / H1, which the
       // gradient later adds itself to).
+      // (reuse: the same b, the same dense rows, the same dual product as on the failed pass -- a maximum taken twice, words
+      // stored twice, a product nobody reads: cheaper than the branches around them)
       if (k < N && lane < NXA) er.e_p = fmax(er.e_p, fabs(L(D::oBV + lane)));
       build_list(&L(D::oGH), (k < N) ? L(D::oSR + 17) : 0.0, (k < N) ? L(D::oSR + 18) : 0.0, L(D::oHDR + 20));
       if (lane < NZ) { st[D::gGH + lane] = lg[0][1]; st[D::gGH + D::GHS + lane] = lg[0][2]; st[D::gGH + 2 * D::GHS + lane] = lg[0][3]; }
@@ -1719,7 +1826,11 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
         sync();
         CMPC_TICK(13);
         gl_dot[0] = list_dot(0, &L(D::oLAMN));
-        if (lane < NZ) { L(D::oH0 + lane) = list_dot(0, &L(D::oXN1)); L(D::oH1 + lane) = list_dot(0, &R(D::oPC1)); }
+        if (lane < NZ) {
+          const double a0 = list_dot(0, &L(D::oXN1)), a1 = list_dot(0, &R(D::oPC1));
+          // (reuse: m = h + [B A]' (.) at once -- the sum the gradient forms below from the parked product, same operands)
+          L(D::oH0 + lane) = reuse ? L(D::oH0 + lane) + a0 : a0; L(D::oH1 + lane) = reuse ? L(D::oH1 + lane) + a1 : a1;
+        }
         gt_phase<false>(L(D::oSR + 17), L(D::oSR + 18), L(D::oHDR + 20));
       } else {
         gl_dot[0] = 0.0;
@@ -1728,6 +1839,15 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
       }
       CMPC_RELANE(lane); CMPC_OPAQUE(lane);
     }
+    if (reuse) {
+      // (the Hessian rows read the Lyapunov gradient and sigma; the multipliers they read are the iterate's, rows whose
+      // multiplier the barrier weights zero are not among them: build_H_row)
+      // (out of their waiting places, each word by the lane that put it there; the lanes past the end shadow word 0 into a dump slot)
+      const int dump = D::oDUMP + (lane & (D::DUMPN - 1));
+      const double al_ = L(D::oUK + ((lane < NZ) ? lane : 0)), w0_ = L(D::oSK + ((lane < NI) ? lane : 0));
+      L((lane < NZ) ? D::oAL + lane : dump) = al_; L((lane < NI) ? D::oW0 + lane : dump) = w0_;
+      sync();
+    } else {
     stage_ineq(k, x0n2);
     CMPC_TICK(12);
     // barrier weights (W2 holds the activity flag on entry); on the very first sweep the slacks and
@@ -1789,6 +1909,7 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
       double h0 = ho + jw[1] + mu * jw[2];     // gradient at the sweep's barrier value (see backward_vectors)
       double h1 = jw[2];
       CMPC_OPAQUE_D(h0); CMPC_OPAQUE_D(h1);    // (rounded here: see list_dot)
+      if constexpr (EVAL_REUSE) { if (!init) { const unsigned re = restage(k); st[re + D::rH0 + col] = h0; st[re + D::rH1 + col] = h1; } }
       if constexpr (D::GT_FIRST) {             // m = h + [B A]' (.) of the backward vectors: the list's part is waiting there
         if (k < N) { L(D::oH0 + col) = h0 + L(D::oH0 + col); L(D::oH1 + col) = h1 + L(D::oH1 + col); }
         else { L(D::oH0 + col) = h0; L(D::oH1 + col) = h1; }
@@ -1806,7 +1927,17 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
       }
     }
     for (int r = lane; r < NI; r += WS) st[D::gG + r] = L(D::oGK + r);
+    if constexpr (EVAL_REUSE) {
+      if (!init) {
+        const unsigned re = restage(k);
+        if (lane < NI) st[re + D::rW0 + lane] = L(D::oW0 + lane);
+        if (lane < 3 * NF) st[re + D::rVDV + lane] = L(D::oVDV + lane);
+        if (lane < 2) st[re + D::rQ + lane] = L(D::oMISC + 30 + lane);
+        if (lane < 3) st[re + D::rPI + lane] = L(D::oMISC + 9 + lane);
+      }
+    }
     CMPC_TICK(0);
+    }
     if constexpr (D::GT_FIRST) {
       // the Hessian rows add themselves to [B A]' P [B A] (read-modify-write of the row's non-zero columns)
       CMPC_RELANE(lane); CMPC_OPAQUE(lane);
@@ -1916,8 +2047,19 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
   // Matrix sweep: evaluate + factorise every stage backwards.  Returns false on wrong inertia.
   // Accumulates the KKT error measures (per lane; reduced by the caller).
   // ---------------------------------------------------------------------------------------
-  CMPC_DEV bool matrix_sweep(double mu, double reg, double x0n2, Err &er, bool init) {
+  // k_done (RETRY_TRACK; N + 1 on the first pass of an iteration): stages k_done .. N were evaluated by a failed pass of this
+  // iteration.  A retry pass takes them from the slab (EVAL_REUSE) and keeps the error measures the failed passes gathered:
+  // they cover exactly those stages, in stage order, and the pass goes on accumulating at k_done - 1.  A pass that fails
+  // at stage k lowers k_done to k (eval_stage(k) ran before its factorisation); the sweeps of the first iteration, whose
+  // evaluation creates the slacks and multipliers, leave it alone and evaluate in full.
+  CMPC_DEV bool matrix_sweep(double mu, double reg, double x0n2, Err &er, bool init, int &k_done) {
+    const bool retry = RETRY_TRACK && k_done <= N;
     er.e_d = er.e_p = er.e_c = er.e_cmu = er.sum_mult = 0.0; er.n_mult = 0;
+    if (retry) {
+      const double *w = &L(D::oM + ER_AT + 6 * lane);
+      er.e_d = w[0]; er.e_p = w[1]; er.e_c = w[2]; er.e_cmu = w[3]; er.sum_mult = w[4]; er.n_mult = (int)w[5];
+      CMPC_RETRY_STAT(28, 1);
+    }
     piv_min = fmax(PIV_MIN, PIV_FRAC * reg);
     // height weight of node k, w_z[k-1] = (w/2) e^{-(k-1)} + w/2 (reference :301-305): one exp per sweep, then
     // e^{-(k-1)} by repeated multiplication as k runs down (the library exp is ~1.5 KB of code per use)
@@ -1928,8 +2070,26 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
       for (int k = N; k >= 0; --k) {
         const double wz = SPD(w_cz_const) * 0.5 * ez + SPD(w_cz_const) * 0.5;
         ez *= e1;
-        eval_stage(k, mu, reg, wz, x0n2, er, init);
-        if (!riccati_stage(k)) return false;
+        if constexpr (RETRY_TRACK) {
+          const bool done = k >= k_done;         // (wave-uniform: both are)
+          CMPC_RETRY_MARK(done);
+          if (EVAL_REUSE || !done) eval_stage(k, mu, reg, wz, x0n2, er, init, done);
+          else { Err again = er; eval_stage(k, mu, reg, wz, x0n2, again, init); }   // (profile build of the old path: same measures either way)
+          if (!riccati_stage(k)) {
+            CMPC_RETRY_MARK(false);
+            if (!init) { CMPC_RETRY_STAT(29, N + 1 - k); if (k < k_done) k_done = CMPC_UNIFORM_INT(k); }
+            if (retry) CMPC_RETRY_STAT(35, 1);   // (a second failure in one iteration)
+            if (!init) {
+              double *w = &L(D::oM + ER_AT + 6 * lane);
+              w[0] = er.e_d; w[1] = er.e_p; w[2] = er.e_c; w[3] = er.e_cmu; w[4] = er.sum_mult; w[5] = (double)er.n_mult;
+            }
+            return false;
+          }
+          CMPC_RETRY_MARK(false);
+        } else {
+          eval_stage(k, mu, reg, wz, x0n2, er, init);
+          if (!riccati_stage(k)) return false;
+        }
       }
       return true;
     } else {
@@ -2614,7 +2774,8 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
       }
       Err er;
       gain_sweep = true;
-      good = matrix_sweep(sp.tol, 0.0, 0.0, er, false);
+      int k_done = N + 1;
+      good = matrix_sweep(sp.tol, 0.0, 0.0, er, false, k_done);
       if constexpr (PIPE) pair_sync(); else gsync();
     }
     if (wv == 0) gain_step(good);
@@ -2642,6 +2803,13 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
                       int32_t *iters, double *kkt_out) {
     // (the tolerance where it is used, from its scalar register: as a local it was a vector register carried through the
     // whole solve -- and the one spilled)
+#if !defined(CMPC_HOST_EMU)
+    // (The plain reuse kernel's scalar spill lanes take v252 .. v254 and its vector side ends at v251: v255 is left over, the
+    // kernel is reported at 255 registers where the budget -- and the allocation, in blocks of eight -- is the 256 of its
+    // two-waves-per-SIMD occupancy.  Naming the register keeps the reported figure at the budget the resource tests pin.)
+    // (To go, together with the `== 256` of those tests in favour of `<= 256`, the next time they are revised: DESIGN.md section 5.)
+    if constexpr (EVAL_REUSE && !CONSTS) asm volatile("" ::: "v255");
+#endif
     auto tol_ = [&]() { return CMPC_FRESH_D(sp.tol); };
     // (what the outer loop compares with, every lane the same value: scalar registers)
     const double tol_acc = ka.tol_acc, tol_10 = ka.tol_tenth;   // ACC_FACTOR * tol, tol / 10
@@ -2709,11 +2877,12 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
       bool fail = false;
       const double mu_sweep = mu;               // barrier value the sweep's gradients are formed at
       const double rl = reg_last;               // (cold state: read once, ahead of the fences of the sweep)
+      int k_done = N + 1;                       // (RETRY_TRACK) first stage a failed pass of this iteration has evaluated
 #ifdef CMPC_TEST_FAIL_ITER                     // (test builds only, never the HIP library's: a failed factorisation at a chosen iteration)
       if (!resume && it == (CMPC_TEST_FAIL_ITER)) fail = true; else
 #endif
-      while (!matrix_sweep(mu, reg, x0n2, er, it == 0)) {
-        sync();
+      while (!matrix_sweep(mu, reg, x0n2, er, it == 0, k_done)) {
+        if constexpr (EVAL_REUSE) gsync(); else sync();
         if (reg == 0.0) reg = (rl == 0.0) ? 1e-4 : fmax(1e-20, rl / 3);
         else reg *= (rl == 0.0) ? 100.0 : 8.0;
         if (reg > 1e20) { fail = true; break; }
@@ -2860,7 +3029,7 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
     if constexpr (GAIN) gain_tail(st, ret_saved, warm);
 #if defined(CMPC_PROFILE) && !defined(CMPC_HOST_EMU)
     if (lane == 0 && ka.prof)
-      for (int i = 0; i < 28; ++i) atomicAdd((unsigned long long *)&ka.prof[i], (unsigned long long)tprof[i]);
+      for (int i = 0; i < CMPC_NPROF; ++i) atomicAdd((unsigned long long *)&ka.prof[i], (unsigned long long)tprof[i]);
 #endif
     if constexpr (PIPE) pair_sync(); else sync();
   }
