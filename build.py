@@ -14,44 +14,56 @@ def _newer(target, sources):
     return any(os.path.getmtime(s) > t for s in sources)
 
 
-def build_hip(force=False, verbose=False):
-    src = os.path.join(PKG, "csrc", "cmpc_hip.hip")
-    wbc = os.path.join(PKG, "csrc", "wbc_qp.hip")          # batched whole-body QP (include/cmpc_wbc.h), same library
-    deps = [src, wbc, os.path.join(PKG, "csrc", "cmpc_kernel.hpp"), os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp"), os.path.join(PKG, "csrc", "cmpc_order_fit.h"),
-            os.path.join(ROOT, "include", "cmpc.h"), os.path.join(ROOT, "include", "cmpc_wbc.h")]
-    out = os.path.join(PKG, "libcmpc_amd.so")
-    if force or _newer(out, deps):
-        cmd = ["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", out, src, wbc]
-        if verbose:
-            cmd.insert(1, "-Rpass-analysis=kernel-resource-usage")
-        subprocess.check_call(cmd)
+CSRC = os.path.join(PKG, "csrc")
+# the solver's device source, which the host emulation and the device unit harness compile as well
+KERNEL_DEPS = [os.path.join(CSRC, "cmpc_kernel.hpp"), os.path.join(CSRC, "cmpc_lds_asm.hpp"), os.path.join(CSRC, "cmpc_wave.hpp"),
+               os.path.join(ROOT, "include", "cmpc.h")]
+# everything the HIP library (and each of its diagnostic variants) is built from; the first two are the translation units:
+# the solver and the batched whole-body QP (include/cmpc_wbc.h), same library
+DEVICE_DEPS = [os.path.join(CSRC, "cmpc_hip.hip"), os.path.join(CSRC, "wbc_qp.hip")] + KERNEL_DEPS + [
+    os.path.join(CSRC, "cmpc_order_fit.h"), os.path.join(ROOT, "include", "cmpc_wbc.h")]
+EMU_DIR = os.path.join(ROOT, "tests", "emu")
+
+
+def _hipcc_lib(out, defines=(), force=False, verbose=False):
+    if force or _newer(out, DEVICE_DEPS):
+        subprocess.check_call(["hipcc"] + (["-Rpass-analysis=kernel-resource-usage"] if verbose else [])
+                              + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared"]
+                              + ["-D" + d for d in defines] + ["-o", out] + DEVICE_DEPS[:2])
     return out
+
+
+def _emu_lib(src, out, defines=(), force=False):
+    src, out = os.path.join(EMU_DIR, src), os.path.join(EMU_DIR, out)
+    if force or _newer(out, [src, os.path.join(EMU_DIR, "cmpc_emu.cpp")] + KERNEL_DEPS):
+        # (-mfma -ffp-contract=off: the kernel's explicit CMPC_FMA are single instructions, and nothing else is fused)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-fPIC", "-shared", "-pthread"]
+                              + ["-D" + d for d in defines] + ["-o", out, src])
+    return out
+
+
+def build_hip(force=False, verbose=False):
+    return _hipcc_lib(os.path.join(PKG, "libcmpc_amd.so"), force=force, verbose=verbose)
 
 
 def build_hip_profile(force=False):
     """Diagnostic variant with in-kernel phase timers (tools/ only; never loaded by the package)."""
-    src = os.path.join(PKG, "csrc", "cmpc_hip.hip")
-    deps = [src, os.path.join(PKG, "csrc", "cmpc_kernel.hpp"), os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp"),
-            os.path.join(ROOT, "include", "cmpc.h")]
-    out = os.path.join(ROOT, "tools", "libcmpc_amd_prof.so")
-    if force or _newer(out, deps):
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                               "-DCMPC_PROFILE", "-o", out, src, os.path.join(PKG, "csrc", "wbc_qp.hip")])
-    return out
+    return _hipcc_lib(os.path.join(ROOT, "tools", "libcmpc_amd_prof.so"), ["CMPC_PROFILE"], force)
 
 
 def build_hip_dev(force=False):
     """Developer variant (tools/ only; never loaded by the package unless CMPC_LIB_PATH names it): -DCMPC_DEV_KNOBS compiles
     in the environment knobs of the occupancy / kernel-choice studies (CMPC_WG_PER_CU, CMPC_PAIR, CMPC_PAIR_PER_CU), which
     the shipped library does not read."""
-    src = os.path.join(PKG, "csrc", "cmpc_hip.hip")
-    deps = [src, os.path.join(PKG, "csrc", "cmpc_kernel.hpp"), os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp"),
-            os.path.join(ROOT, "include", "cmpc.h")]
-    out = os.path.join(ROOT, "tools", "libcmpc_amd_dev.so")
-    if force or _newer(out, deps):
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                               "-DCMPC_DEV_KNOBS", "-o", out, src, os.path.join(PKG, "csrc", "wbc_qp.hip")])
-    return out
+    return _hipcc_lib(os.path.join(ROOT, "tools", "libcmpc_amd_dev.so"), ["CMPC_DEV_KNOBS"], force)
+
+
+def build_hip_no_reuse(force=False, profile=False):
+    """Diagnostic variant (tools/ only; loaded through CMPC_LIB_PATH): -DCMPC_NO_EVAL_REUSE, the one-wave 4-vertex kernel that
+    evaluates every stage of a retry pass again -- the third leg of the A/B runs, and with profile=True the `before` of
+    tools/phase_profile.py's retry figures."""
+    return _hipcc_lib(os.path.join(ROOT, "tools", "libcmpc_amd_noreuse_prof.so" if profile else "libcmpc_amd_noreuse.so"),
+                      ["CMPC_NO_EVAL_REUSE"] + (["CMPC_PROFILE"] if profile else []), force)
 
 
 def build_oracle(force=False):
@@ -64,74 +76,31 @@ def build_oracle(force=False):
 
 
 def build_emu(force=False):
-    src = os.path.join(ROOT, "tests", "emu", "cmpc_emu.cpp")
-    out = os.path.join(ROOT, "tests", "emu", "libcmpc_emu.so")
-    deps = [src, os.path.join(PKG, "csrc", "cmpc_kernel.hpp"), os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp"),
-            os.path.join(ROOT, "include", "cmpc.h")]
-    if force or _newer(out, deps):
-        # (-mfma -ffp-contract=off: the kernel's explicit CMPC_FMA are single instructions, and nothing else is fused)
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-o", out, src])
-    return out
+    return _emu_lib("cmpc_emu.cpp", "libcmpc_emu.so", force=force)
 
 
 def build_emu_gain(force=False):
     """Host emulation of the gain variant of the solver (tests/emu/cmpc_emu_gain.cpp): test harness only."""
-    src = os.path.join(ROOT, "tests", "emu", "cmpc_emu_gain.cpp")
-    out = os.path.join(ROOT, "tests", "emu", "libcmpc_emu_gain.so")
-    deps = [src, os.path.join(ROOT, "tests", "emu", "cmpc_emu.cpp"), os.path.join(PKG, "csrc", "cmpc_kernel.hpp"),
-            os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp"),
-            os.path.join(ROOT, "include", "cmpc.h")]
-    if force or _newer(out, deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-o", out, src])
-    return out
+    return _emu_lib("cmpc_emu_gain.cpp", "libcmpc_emu_gain.so", force=force)
 
 
 def build_emu_consts(force=False):
     """Host emulation of the solver with per-instance constants (tests/emu/cmpc_emu_consts.cpp): test harness only."""
-    src = os.path.join(ROOT, "tests", "emu", "cmpc_emu_consts.cpp")
-    out = os.path.join(ROOT, "tests", "emu", "libcmpc_emu_consts.so")
-    deps = [src, os.path.join(ROOT, "tests", "emu", "cmpc_emu.cpp"), os.path.join(PKG, "csrc", "cmpc_kernel.hpp"),
-            os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp"),
-            os.path.join(ROOT, "include", "cmpc.h")]
-    if force or _newer(out, deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-fPIC", "-shared", "-pthread", "-o", out, src])
-    return out
+    return _emu_lib("cmpc_emu_consts.cpp", "libcmpc_emu_consts.so", force=force)
 
 
 def build_emu_reuse(force=False, reuse=True):
     """Host emulation with counters on the retried factorisations (tests/emu/cmpc_emu_reuse.cpp): test harness only.
     reuse=False builds the kernel source with -DCMPC_NO_EVAL_REUSE, the path that evaluates every stage of a retry pass again."""
-    src = os.path.join(ROOT, "tests", "emu", "cmpc_emu_reuse.cpp")
-    out = os.path.join(ROOT, "tests", "emu", "libcmpc_emu_reuse.so" if reuse else "libcmpc_emu_noreuse.so")
-    deps = [src, os.path.join(ROOT, "tests", "emu", "cmpc_emu.cpp"), os.path.join(PKG, "csrc", "cmpc_kernel.hpp"),
-            os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp"),
-            os.path.join(ROOT, "include", "cmpc.h")]
-    if force or _newer(out, deps):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-fPIC", "-shared", "-pthread"]
-                              + ([] if reuse else ["-DCMPC_NO_EVAL_REUSE"]) + ["-o", out, src])
-    return out
-
-
-def build_hip_no_reuse(force=False, profile=False):
-    """Diagnostic variant (tools/ only; loaded through CMPC_LIB_PATH): -DCMPC_NO_EVAL_REUSE, the one-wave 4-vertex kernel that
-    evaluates every stage of a retry pass again -- the third leg of the A/B runs, and with profile=True the `before` of
-    tools/phase_profile.py's retry figures."""
-    src = os.path.join(PKG, "csrc", "cmpc_hip.hip")
-    deps = [src, os.path.join(PKG, "csrc", "cmpc_kernel.hpp"), os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp"),
-            os.path.join(ROOT, "include", "cmpc.h")]
-    out = os.path.join(ROOT, "tools", "libcmpc_amd_noreuse_prof.so" if profile else "libcmpc_amd_noreuse.so")
-    if force or _newer(out, deps):
-        subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-DCMPC_NO_EVAL_REUSE"]
-                              + (["-DCMPC_PROFILE"] if profile else []) + ["-o", out, src, os.path.join(PKG, "csrc", "wbc_qp.hip")])
-    return out
+    return _emu_lib("cmpc_emu_reuse.cpp", "libcmpc_emu_reuse.so" if reuse else "libcmpc_emu_noreuse.so",
+                    [] if reuse else ["CMPC_NO_EVAL_REUSE"], force)
 
 
 def build_device_unit(force=False):
     """GPU-tier unit harness for the device-only primitives (tests/gpu_unit): never loaded by the package."""
     src = os.path.join(ROOT, "tests", "gpu_unit", "cmpc_device_unit.hip")
     out = os.path.join(ROOT, "tests", "gpu_unit", "libcmpc_device_unit.so")
-    deps = [src, os.path.join(PKG, "csrc", "cmpc_kernel.hpp"), os.path.join(PKG, "csrc", "cmpc_lds_asm.hpp"), os.path.join(PKG, "csrc", "cmpc_wave.hpp")]
-    if force or _newer(out, deps):
+    if force or _newer(out, [src] + KERNEL_DEPS):
         subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-o", out, src])
     return out
 

@@ -114,33 +114,46 @@ __global__ void __launch_bounds__(256) cmpc_order_scatter_kernel(int B, const in
   order[base[b] + atomicAdd(counters + 3 + ORDER_BUCKETS + b, 1)] = i;
 }
 
-// One workgroup per instance in flight: a single wave for the 4-vertex solver, NW = WAVES_NV8 waves for the 8-vertex
-// one (its stage block has 92 rows: with 128 lanes every row / column has its own lane, cmpc_kernel.hpp).
-template <int NV, int NW>
-__global__ void __launch_bounds__(64 * NW, (NV == 4 ? CMPC_WAVES_PER_SIMD : 1)) cmpc_solve_kernel(cmpc::KArgs ka, int *ticket,
-                                                                                                   const int *__restrict__ order) {
-  using D = cmpc::Dims<NV, NW>;
-  __shared__ __attribute__((aligned(16))) double lds[D::LDS_DOUBLES];
+// The instance loop of every solver kernel: one workgroup per instance in flight -- a single wave for the 4-vertex
+// solver, NW = WAVES_NV8 waves for the 8-vertex one (its stage block has 92 rows: with 128 lanes every row / column has its
+// own lane, cmpc_kernel.hpp), the pipelined pair of waves with PIPE -- draws tickets until the batch is drained and hands
+// each instance to cmpc::run_instance.  GAIN / CONSTS: the variant of the solver (gain, gbuf / consts: see there; null in
+// the kernels without them).
+template <int NV, int NW, bool PIPE, bool GAIN, bool CONSTS>
+__device__ __forceinline__ void cmpc_instance_loop(const cmpc::KArgs &ka, double *gain, double *gbuf, const double *__restrict__ consts,
+                                                   int *ticket, const int *__restrict__ order) {
+  using D = cmpc::Dims<NV, NW, PIPE>;
+  __shared__ __attribute__((aligned(16))) double lds[(PIPE ? 2 : 1) * D::LDS_DOUBLES];    // (the pair: two LDS images)
   __shared__ int next;
   double *slab = ka.scratch + (size_t)blockIdx.x * ka.scratch_stride;
-  const size_t nrec = CMPC_NREC(ka.sp.N), nsol = CMPC_NSOL(ka.sp.N, NV), nstate = CMPC_NSTATE(ka.sp.N, NV);
   for (;;) {
+    int tid;
     // (single-wave workgroups: the lane id from the execution mask, re-derived per instance, instead of threadIdx.x kept
     // live -- and spilled -- across the whole solve)
-    const int tid = (NW == 1) ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : (int)threadIdx.x;
+    if constexpr (NW == 1 && !PIPE) tid = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+    else tid = (int)threadIdx.x;
     if (tid == 0) next = atomicAdd(ticket, 1);
     __syncthreads();
-    const int tk = next;
+    int tk;
+    // (CONSTS: the ticket is wave-uniform and said so before the exit test: a loop whose exit the compiler takes for divergent
+    // turns every per-instance address that crosses the refusal branch -- record, row, outputs -- into a vector register)
+    if constexpr (CONSTS) tk = __builtin_amdgcn_readfirstlane(next);
+    else tk = next;
     __syncthreads();
     if (tk >= ka.B) break;                      // every wave reaches this exit
     // the queue position comes out of LDS in a vector register; the instance index is wave-uniform, and saying so
     // keeps the record / output base addresses in scalar registers
-    const int p = __builtin_amdgcn_readfirstlane(order[__builtin_amdgcn_readfirstlane(tk)]);
-    cmpc::Solver<NV, NW> s(ka, lds, slab, ka.recs + (size_t)p * nrec);
-    s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr,
-            ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr, ka.out + (size_t)p * nsol, ka.status + p,
-            ka.iters + p, ka.kkt + p);
+    int p;
+    if constexpr (CONSTS) p = __builtin_amdgcn_readfirstlane(order[tk]);
+    else p = __builtin_amdgcn_readfirstlane(order[__builtin_amdgcn_readfirstlane(tk)]);
+    cmpc::run_instance<NV, NW, PIPE, GAIN, CONSTS>(ka, lds, slab, p, (int)blockIdx.x, gain, gbuf, consts);
   }
+}
+
+template <int NV, int NW>
+__global__ void __launch_bounds__(64 * NW, (NV == 4 ? CMPC_WAVES_PER_SIMD : 1)) cmpc_solve_kernel(cmpc::KArgs ka, int *ticket,
+                                                                                                   const int *__restrict__ order) {
+  cmpc_instance_loop<NV, NW, false, false, false>(ka, nullptr, nullptr, nullptr, ticket, order);
 }
 
 // The pipelined pair (cmpc::Solver<4, 1, true>): two waves per instance, two LDS images.  For batches that do not keep
@@ -149,141 +162,37 @@ __global__ void __launch_bounds__(64 * NW, (NV == 4 ? CMPC_WAVES_PER_SIMD : 1)) 
 template <int NV, int WPS>
 __global__ void __launch_bounds__(128, WPS) cmpc_solve_pair_kernel(cmpc::KArgs ka, int *ticket,
                                                                                   const int *__restrict__ order) {
-  using D = cmpc::Dims<NV, 1, true>;
-  __shared__ __attribute__((aligned(16))) double lds[2 * D::LDS_DOUBLES];
-  __shared__ int next;
-  double *slab = ka.scratch + (size_t)blockIdx.x * ka.scratch_stride;
-  const size_t nrec = CMPC_NREC(ka.sp.N), nsol = CMPC_NSOL(ka.sp.N, NV), nstate = CMPC_NSTATE(ka.sp.N, NV);
-  for (;;) {
-    if (threadIdx.x == 0) next = atomicAdd(ticket, 1);
-    __syncthreads();
-    const int tk = next;
-    __syncthreads();
-    if (tk >= ka.B) break;                      // both waves reach this exit
-    const int p = __builtin_amdgcn_readfirstlane(order[__builtin_amdgcn_readfirstlane(tk)]);
-    cmpc::Solver<NV, 1, true> s(ka, lds, slab, ka.recs + (size_t)p * nrec);
-    s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr,
-            ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr, ka.out + (size_t)p * nsol, ka.status + p,
-            ka.iters + p, ka.kkt + p);
-  }
+  cmpc_instance_loop<NV, 1, true, false, false>(ka, nullptr, nullptr, nullptr, ticket, order);
 }
 
-// Gain variants (cmpc_solve_batch_gain): the loops above with Solver<..., GAIN = true> -- the solve is the same, and the
-// first-stage gain follows it (cmpc_kernel.hpp, Solver::gain_tail).  Kernels of their own, so that the plain ones are
-// left as they are.  gain [B][CMPC_NGAIN(nv)]; gbuf: the saved iterate of each workgroup (CMPC_NSTATE doubles).
+// Gain variants (cmpc_solve_batch_gain): Solver<..., GAIN = true> -- the solve is the same, and the first-stage gain
+// follows it (cmpc_kernel.hpp, Solver::gain_tail).  Kernels of their own, so that the plain ones are left as they are.
+// gain [B][CMPC_NGAIN(nv)]; gbuf: the saved iterate of each workgroup (CMPC_NSTATE doubles).
 template <int NV, int NW>
 __global__ void __launch_bounds__(64 * NW, (NV == 4 ? CMPC_WAVES_PER_SIMD : 1)) cmpc_solve_gain_kernel(cmpc::KArgs ka, double *gain,
                                                                                                         double *gbuf, int *ticket,
                                                                                                         const int *__restrict__ order) {
-  using D = cmpc::Dims<NV, NW>;
-  __shared__ __attribute__((aligned(16))) double lds[D::LDS_DOUBLES];
-  __shared__ int next;
-  double *slab = ka.scratch + (size_t)blockIdx.x * ka.scratch_stride;
-  const size_t nrec = CMPC_NREC(ka.sp.N), nsol = CMPC_NSOL(ka.sp.N, NV), nstate = CMPC_NSTATE(ka.sp.N, NV);
-  for (;;) {
-    const int tid = (NW == 1) ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : (int)threadIdx.x;
-    if (tid == 0) next = atomicAdd(ticket, 1);
-    __syncthreads();
-    const int tk = next;
-    __syncthreads();
-    if (tk >= ka.B) break;
-    const int p = __builtin_amdgcn_readfirstlane(order[__builtin_amdgcn_readfirstlane(tk)]);
-    cmpc::Solver<NV, NW, false, true> s(ka, lds, slab, ka.recs + (size_t)p * nrec);
-    s.gain_out = gain + (size_t)p * CMPC_NGAIN(NV);
-    s.gbuf = cmpc::GArr{gbuf + (size_t)blockIdx.x * nstate};
-    s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr,
-            ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr, ka.out + (size_t)p * nsol, ka.status + p,
-            ka.iters + p, ka.kkt + p);
-  }
+  cmpc_instance_loop<NV, NW, false, true, false>(ka, gain, gbuf, nullptr, ticket, order);
 }
 
 template <int NV, int WPS>
 __global__ void __launch_bounds__(128, WPS) cmpc_solve_pair_gain_kernel(cmpc::KArgs ka, double *gain, double *gbuf, int *ticket,
                                                                         const int *__restrict__ order) {
-  using D = cmpc::Dims<NV, 1, true>;
-  __shared__ __attribute__((aligned(16))) double lds[2 * D::LDS_DOUBLES];
-  __shared__ int next;
-  double *slab = ka.scratch + (size_t)blockIdx.x * ka.scratch_stride;
-  const size_t nrec = CMPC_NREC(ka.sp.N), nsol = CMPC_NSOL(ka.sp.N, NV), nstate = CMPC_NSTATE(ka.sp.N, NV);
-  for (;;) {
-    if (threadIdx.x == 0) next = atomicAdd(ticket, 1);
-    __syncthreads();
-    const int tk = next;
-    __syncthreads();
-    if (tk >= ka.B) break;
-    const int p = __builtin_amdgcn_readfirstlane(order[__builtin_amdgcn_readfirstlane(tk)]);
-    cmpc::Solver<NV, 1, true, true> s(ka, lds, slab, ka.recs + (size_t)p * nrec);
-    s.gain_out = gain + (size_t)p * CMPC_NGAIN(NV);
-    s.gbuf = cmpc::GArr{gbuf + (size_t)blockIdx.x * nstate};
-    s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr,
-            ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr, ka.out + (size_t)p * nsol, ka.status + p,
-            ka.iters + p, ka.kkt + p);
-  }
+  cmpc_instance_loop<NV, 1, true, true, false>(ka, gain, gbuf, nullptr, ticket, order);
 }
 
-// Per-instance constants (cmpc_solve_batch_consts): the loops above with Solver<..., CONSTS = true>.  consts
-// [B][CMPC_NCONST]: row p belongs to instance p, the wave-uniform index the loop already forms, so the row's address is in
-// scalar registers and its entries are scalar loads.  A row the solver cannot work with (cmpc::consts_row_ok) is answered
-// without a solve.  Kernels of their own, so that the plain ones are left as they are.
+// Per-instance constants (cmpc_solve_batch_consts): Solver<..., CONSTS = true>, consts [B][CMPC_NCONST] (cmpc::run_instance
+// reads, checks and refuses the rows).  Kernels of their own, so that the plain ones are left as they are.
 template <int NV, int NW>
 __global__ void __launch_bounds__(64 * NW, (NV == 4 ? CMPC_WAVES_PER_SIMD : 1)) cmpc_solve_consts_kernel(cmpc::KArgs ka, const double *__restrict__ consts,
                                                                                                           int *ticket, const int *__restrict__ order) {
-  using D = cmpc::Dims<NV, NW>;
-  __shared__ __attribute__((aligned(16))) double lds[D::LDS_DOUBLES];
-  __shared__ int next;
-  double *slab = ka.scratch + (size_t)blockIdx.x * ka.scratch_stride;
-  const size_t nrec = CMPC_NREC(ka.sp.N), nsol = CMPC_NSOL(ka.sp.N, NV), nstate = CMPC_NSTATE(ka.sp.N, NV);
-  for (;;) {
-    const int tid = (NW == 1) ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : (int)threadIdx.x;
-    if (tid == 0) next = atomicAdd(ticket, 1);
-    __syncthreads();
-    // (the ticket is wave-uniform and said so before the exit test: a loop whose exit the compiler takes for divergent turns
-    // every per-instance address that crosses the refusal branch -- record, row, outputs -- into a vector register)
-    const int tk = __builtin_amdgcn_readfirstlane(next);
-    __syncthreads();
-    if (tk >= ka.B) break;
-    const int p = __builtin_amdgcn_readfirstlane(order[tk]);
-    cmpc::Solver<NV, NW, false, false, true> s(ka, lds, slab, ka.recs + (size_t)p * nrec);
-    s.crow = CMPC_CROW(consts + (size_t)p * CMPC_NCONST);
-    double *so = ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr;
-    // (the verdict on the row is the same in every lane; said so, the refusal is a uniform branch and the per-instance
-    // addresses -- record, row, outputs -- stay in scalar registers across it)
-    if (CMPC_UNIFORM_INT((int)cmpc::consts_row_ok(s.crow)))
-      s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr, so,
-              ka.out + (size_t)p * nsol, ka.status + p, ka.iters + p, ka.kkt + p);
-    else
-      s.reject(so, ka.out + (size_t)p * nsol, ka.status + p, ka.iters + p, ka.kkt + p);
-  }
+  cmpc_instance_loop<NV, NW, false, false, true>(ka, nullptr, nullptr, consts, ticket, order);
 }
 
 template <int NV, int WPS>
 __global__ void __launch_bounds__(128, WPS) cmpc_solve_pair_consts_kernel(cmpc::KArgs ka, const double *__restrict__ consts, int *ticket,
                                                                           const int *__restrict__ order) {
-  using D = cmpc::Dims<NV, 1, true>;
-  __shared__ __attribute__((aligned(16))) double lds[2 * D::LDS_DOUBLES];
-  __shared__ int next;
-  double *slab = ka.scratch + (size_t)blockIdx.x * ka.scratch_stride;
-  const size_t nrec = CMPC_NREC(ka.sp.N), nsol = CMPC_NSOL(ka.sp.N, NV), nstate = CMPC_NSTATE(ka.sp.N, NV);
-  for (;;) {
-    if (threadIdx.x == 0) next = atomicAdd(ticket, 1);
-    __syncthreads();
-    // (the ticket is wave-uniform and said so before the exit test: a loop whose exit the compiler takes for divergent turns
-    // every per-instance address that crosses the refusal branch -- record, row, outputs -- into a vector register)
-    const int tk = __builtin_amdgcn_readfirstlane(next);
-    __syncthreads();
-    if (tk >= ka.B) break;
-    const int p = __builtin_amdgcn_readfirstlane(order[tk]);
-    cmpc::Solver<NV, 1, true, false, true> s(ka, lds, slab, ka.recs + (size_t)p * nrec);
-    s.crow = CMPC_CROW(consts + (size_t)p * CMPC_NCONST);
-    double *so = ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr;
-    // (the verdict on the row is the same in every lane; said so, the refusal is a uniform branch and the per-instance
-    // addresses -- record, row, outputs -- stay in scalar registers across it)
-    if (CMPC_UNIFORM_INT((int)cmpc::consts_row_ok(s.crow)))
-      s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr, so,
-              ka.out + (size_t)p * nsol, ka.status + p, ka.iters + p, ka.kkt + p);
-    else
-      s.reject(so, ka.out + (size_t)p * nsol, ka.status + p, ka.iters + p, ka.kkt + p);
-  }
+  cmpc_instance_loop<NV, 1, true, false, true>(ka, nullptr, nullptr, consts, ticket, order);
 }
 
 // One workgroup per record (grid-stride over the batch), one lane per pair of output words: each
@@ -544,8 +453,39 @@ int cmpc_solve_batch(cmpc_handle *h, int32_t B, const double *params, const doub
 
 }  // extern "C"
 
+// The solver kernels: what cmpc_solve_batch_state, _gain and _consts launch (rows; never gain and consts both: there is no
+// gain variant with per-instance constants), by shape (columns): the pipelined pair, the one-wave 4-vertex kernel, the
+// 8-vertex one and -- developer build -- the pair built for one wave per SIMD.  name: what cmpc_last_kernel_name reports.
+struct SolverKernel { const void *fn; int block; const char *name; };
+enum { VARIANT_PLAIN, VARIANT_GAIN, VARIANT_CONSTS };
+enum { SHAPE_PAIR, SHAPE_NV4, SHAPE_NV8, SHAPE_PAIR_WPS1 };
+static_assert(cmpc::WAVES_NV8 == 2, "the names of the 8-vertex kernels");
+static const SolverKernel solver_kernels[3][4] = {
+    {{(const void *)cmpc_solve_pair_kernel<4, 2>, 128, "cmpc_solve_pair_kernel<4, 2>"},
+     {(const void *)cmpc_solve_kernel<4, 1>, 64, "cmpc_solve_kernel<4, 1>"},
+     {(const void *)cmpc_solve_kernel<8, cmpc::WAVES_NV8>, 64 * cmpc::WAVES_NV8, "cmpc_solve_kernel<8, 2>"},
+#ifdef CMPC_DEV_KNOBS
+     {(const void *)cmpc_solve_pair_kernel<4, 1>, 128, "cmpc_solve_pair_kernel<4, 1>"},
+#endif
+    },
+    {{(const void *)cmpc_solve_pair_gain_kernel<4, 2>, 128, "cmpc_solve_pair_gain_kernel<4, 2>"},
+     {(const void *)cmpc_solve_gain_kernel<4, 1>, 64, "cmpc_solve_gain_kernel<4, 1>"},
+     {(const void *)cmpc_solve_gain_kernel<8, cmpc::WAVES_NV8>, 64 * cmpc::WAVES_NV8, "cmpc_solve_gain_kernel<8, 2>"},
+#ifdef CMPC_DEV_KNOBS
+     {(const void *)cmpc_solve_pair_gain_kernel<4, 1>, 128, "cmpc_solve_pair_gain_kernel<4, 1>"},
+#endif
+    },
+    {{(const void *)cmpc_solve_pair_consts_kernel<4, 2>, 128, "cmpc_solve_pair_consts_kernel<4, 2>"},
+     {(const void *)cmpc_solve_consts_kernel<4, 1>, 64, "cmpc_solve_consts_kernel<4, 1>"},
+     {(const void *)cmpc_solve_consts_kernel<8, cmpc::WAVES_NV8>, 64 * cmpc::WAVES_NV8, "cmpc_solve_consts_kernel<8, 2>"},
+#ifdef CMPC_DEV_KNOBS
+     {(const void *)cmpc_solve_pair_consts_kernel<4, 1>, 128, "cmpc_solve_pair_consts_kernel<4, 1>"},
+#endif
+    },
+};
+
 // cmpc_solve_batch_state, cmpc_solve_batch_gain and cmpc_solve_batch_consts: gain == nullptr and consts == nullptr launch the
-// plain kernels (never both given: there is no gain variant with per-instance constants)
+// plain kernels
 static int solve_batch(cmpc_handle *h, int32_t B, const double *params, const double *warm_XU, const double *state_in,
                        double *out_XU, double *state_out, int32_t *status, int32_t *iters, double *kkt_res, double *gain,
                        const double *consts, void *stream) {
@@ -570,7 +510,6 @@ static int solve_batch(cmpc_handle *h, int32_t B, const double *params, const do
   ka.scratch = h->scratch; ka.scratch_stride = h->slab_doubles;
   ka.prof = h->prof;
   cmpc::fill_levels(ka);
-  const int grid = B < h->grid ? B : h->grid;
   if (B > h->order_cap) {                       // grows rarely; hipFree / hipMalloc synchronise the device
     if (h->order) (void)hipFree(h->order);
     h->order = nullptr; h->order_cap = 0;
@@ -585,52 +524,17 @@ static int solve_batch(cmpc_handle *h, int32_t B, const double *params, const do
                      mu_word, h->order + B, h->ticket);
   hipLaunchKernelGGL(cmpc_order_scatter_kernel, dim3((B + 255) / 256), dim3(256), 0, st, B, h->order + B, h->order, h->ticket);
   const bool pair = h->spec.nv == 4 && B <= h->pair_max_batch;   // the batch does not fill the GPU for long: two waves per instance
-  const int launch_grid = pair ? (B < h->pair_grid ? B : h->pair_grid) : grid;
-  if (launch_grid > h->slabs) return fail(h, "cmpc_solve_batch: launch grid exceeds the slabs of the handle");
-  if (gain) {
-    if (pair) {
-      const dim3 pg(launch_grid);
+  const int resident = pair ? h->pair_grid : h->grid, grid = B < resident ? B : resident;
+  if (grid > h->slabs) return fail(h, "cmpc_solve_batch: launch grid exceeds the slabs of the handle");
+  int shape = pair ? SHAPE_PAIR : (h->spec.nv == 4) ? SHAPE_NV4 : SHAPE_NV8;
 #ifdef CMPC_DEV_KNOBS
-      if (h->pair_per_cu < 3) { hipLaunchKernelGGL((cmpc_solve_pair_gain_kernel<4, 1>), pg, dim3(128), 0, st, ka, gain, h->gbuf, h->ticket, h->order); h->last_kernel = "cmpc_solve_pair_gain_kernel<4, 1>"; }
-      else
+  if (pair && h->pair_per_cu < 3) shape = SHAPE_PAIR_WPS1;
 #endif
-      { hipLaunchKernelGGL((cmpc_solve_pair_gain_kernel<4, 2>), pg, dim3(128), 0, st, ka, gain, h->gbuf, h->ticket, h->order); h->last_kernel = "cmpc_solve_pair_gain_kernel<4, 2>"; }
-    } else if (h->spec.nv == 4) {
-      hipLaunchKernelGGL((cmpc_solve_gain_kernel<4, 1>), dim3(grid), dim3(64), 0, st, ka, gain, h->gbuf, h->ticket, h->order);
-      h->last_kernel = "cmpc_solve_gain_kernel<4, 1>";
-    } else {
-      hipLaunchKernelGGL((cmpc_solve_gain_kernel<8, cmpc::WAVES_NV8>), dim3(grid), dim3(64 * cmpc::WAVES_NV8), 0, st, ka, gain, h->gbuf, h->ticket, h->order);
-      h->last_kernel = "cmpc_solve_gain_kernel<8, 2>";
-    }
-  } else if (consts) {
-    if (pair) {
-      const dim3 pg(launch_grid);
-#ifdef CMPC_DEV_KNOBS
-      if (h->pair_per_cu < 3) { hipLaunchKernelGGL((cmpc_solve_pair_consts_kernel<4, 1>), pg, dim3(128), 0, st, ka, consts, h->ticket, h->order); h->last_kernel = "cmpc_solve_pair_consts_kernel<4, 1>"; }
-      else
-#endif
-      { hipLaunchKernelGGL((cmpc_solve_pair_consts_kernel<4, 2>), pg, dim3(128), 0, st, ka, consts, h->ticket, h->order); h->last_kernel = "cmpc_solve_pair_consts_kernel<4, 2>"; }
-    } else if (h->spec.nv == 4) {
-      hipLaunchKernelGGL((cmpc_solve_consts_kernel<4, 1>), dim3(grid), dim3(64), 0, st, ka, consts, h->ticket, h->order);
-      h->last_kernel = "cmpc_solve_consts_kernel<4, 1>";
-    } else {
-      hipLaunchKernelGGL((cmpc_solve_consts_kernel<8, cmpc::WAVES_NV8>), dim3(grid), dim3(64 * cmpc::WAVES_NV8), 0, st, ka, consts, h->ticket, h->order);
-      h->last_kernel = "cmpc_solve_consts_kernel<8, 2>";
-    }
-  } else if (pair) {
-    const dim3 pg(launch_grid);
-#ifdef CMPC_DEV_KNOBS
-    if (h->pair_per_cu < 3) { hipLaunchKernelGGL((cmpc_solve_pair_kernel<4, 1>), pg, dim3(128), 0, st, ka, h->ticket, h->order); h->last_kernel = "cmpc_solve_pair_kernel<4, 1>"; }
-    else
-#endif
-    { hipLaunchKernelGGL((cmpc_solve_pair_kernel<4, 2>), pg, dim3(128), 0, st, ka, h->ticket, h->order); h->last_kernel = "cmpc_solve_pair_kernel<4, 2>"; }
-  } else if (h->spec.nv == 4) {
-    hipLaunchKernelGGL((cmpc_solve_kernel<4, 1>), dim3(grid), dim3(64), 0, st, ka, h->ticket, h->order);
-    h->last_kernel = "cmpc_solve_kernel<4, 1>";
-  } else {
-    hipLaunchKernelGGL((cmpc_solve_kernel<8, cmpc::WAVES_NV8>), dim3(grid), dim3(64 * cmpc::WAVES_NV8), 0, st, ka, h->ticket, h->order);
-    h->last_kernel = "cmpc_solve_kernel<8, 2>";
-  }
+  const SolverKernel &k = solver_kernels[gain ? VARIANT_GAIN : consts ? VARIANT_CONSTS : VARIANT_PLAIN][shape];
+  void *args_plain[] = {&ka, &h->ticket, &h->order}, *args_gain[] = {&ka, &gain, &h->gbuf, &h->ticket, &h->order},
+       *args_consts[] = {&ka, &consts, &h->ticket, &h->order};
+  h->last_kernel = k.name;
+  HIP_TRY(h, hipLaunchKernel(k.fn, dim3(grid), dim3(k.block), gain ? args_gain : consts ? args_consts : args_plain, 0, st));
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipEventRecord(h->ev1, st));
   h->timed = true;

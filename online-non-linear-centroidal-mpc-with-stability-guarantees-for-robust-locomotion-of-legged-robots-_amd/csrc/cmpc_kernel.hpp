@@ -3035,5 +3035,33 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
   }
 };
 
+// One instance from its record to its outputs: the body of the instance loop, the same for every solver variant, on the
+// device (cmpc_instance_loop, csrc/cmpc_hip.hip) and in the host emulation (run_batch, tests/emu/cmpc_emu.cpp).  p: the
+// instance (wave-uniform; the caller says so), slot: the workgroup's slab.  gain [B][CMPC_NGAIN(NV)] and gbuf, the saved
+// iterate of every slot (CMPC_NSTATE doubles each): GAIN only; consts [B][CMPC_NCONST]: CONSTS only -- row p belongs to
+// instance p, so the row's address is in scalar registers and its entries are scalar loads, and a row the solver cannot
+// work with (consts_row_ok) is answered without a solve.
+template <int NV, int NW, bool PIPE, bool GAIN, bool CONSTS>
+CMPC_DEV void run_instance(const KArgs &ka, double *lds, double *slab, int p, unsigned slot, double *gain, double *gbuf,
+                           const double *consts) {
+  const size_t nrec = CMPC_NREC(ka.sp.N), nsol = CMPC_NSOL(ka.sp.N, NV), nstate = CMPC_NSTATE(ka.sp.N, NV);
+  Solver<NV, NW, PIPE, GAIN, CONSTS> s(ka, lds, slab, ka.recs + (size_t)p * nrec);
+  if constexpr (GAIN) {
+    s.gain_out = gain + (size_t)p * CMPC_NGAIN(NV);
+    s.gbuf = GArr{gbuf + (size_t)slot * nstate};
+  }
+  if constexpr (CONSTS) s.crow = CMPC_CROW(consts + (size_t)p * CMPC_NCONST);
+  double *so = ka.state_out ? ka.state_out + (size_t)p * nstate : nullptr;
+  // (CONSTS: the verdict on the row is the same in every lane; said so, the refusal is a uniform branch and the per-instance
+  // addresses -- record, row, outputs -- stay in scalar registers across it)
+  bool ok = true;
+  if constexpr (CONSTS) ok = CMPC_UNIFORM_INT((int)consts_row_ok(s.crow));
+  if (ok)
+    s.solve(ka.warm ? ka.warm + (size_t)p * nsol : nullptr, ka.state_in ? ka.state_in + (size_t)p * nstate : nullptr, so,
+            ka.out + (size_t)p * nsol, ka.status + p, ka.iters + p, ka.kkt + p);
+  else
+    s.reject(so, ka.out + (size_t)p * nsol, ka.status + p, ka.iters + p, ka.kkt + p);
+}
+
 #endif  // CMPC_NO_DEVICE_CODE
 }  // namespace cmpc

@@ -88,59 +88,75 @@ static int emu_fail_iter = -1;
 #define CMPC_TEST_FAIL_ITER emu_fail_iter
 #include "../../online-non-linear-centroidal-mpc-with-stability-guarantees-for-robust-locomotion-of-legged-robots-_amd/csrc/cmpc_kernel.hpp"
 
-template <int NV, int NW, bool PIPE = false>
-static void run_batch(const cmpc::KArgs &ka, double *lds) {
-  const cmpc_spec &sp = ka.sp;
-  const size_t nrec = CMPC_NREC(sp.N), nsol = CMPC_NSOL(sp.N, NV), nstate = CMPC_NSTATE(sp.N, NV);
+// The instances of a batch one after the other, each through the kernels' own cmpc::run_instance (one slab, slot 0).
+template <int NV, int NW, bool PIPE, bool GAIN, bool CONSTS>
+static void run_batch(const cmpc::KArgs &ka, double *lds, double *gain, double *gbuf, const double *consts) {
   for (int p = 0; p < ka.B; ++p) {
     std::vector<std::thread> th;
     for (int l = 0; l < 64 * (PIPE ? 2 : NW); ++l)
       th.emplace_back([&, l]() {
         emu_lane_id = l;
-        cmpc::Solver<NV, NW, PIPE> s(ka, lds, ka.scratch, ka.recs + p * nrec);
-        s.solve(ka.warm ? ka.warm + p * nsol : nullptr, ka.state_in ? ka.state_in + p * nstate : nullptr,
-                ka.state_out ? ka.state_out + p * nstate : nullptr, ka.out + p * nsol, ka.status + p, ka.iters + p, ka.kkt + p);
+        cmpc::run_instance<NV, NW, PIPE, GAIN, CONSTS>(ka, lds, ka.scratch, p, 0, gain, gbuf, consts);
       });
     for (auto &t : th) t.join();
   }
 }
 
-extern "C" int cmpc_emu_solve_batch_state(const cmpc_spec *sp, int32_t B, const double *recs, const double *warm,
-                                          const double *state_in, double *out, double *state_out, int32_t *status,
-                                          int32_t *iters, double *kkt);
-extern "C" int cmpc_emu_solve_batch(const cmpc_spec *sp, int32_t B, const double *recs, const double *warm,
-                                    double *out, int32_t *status, int32_t *iters, double *kkt) {
-  return cmpc_emu_solve_batch_state(sp, B, recs, warm, nullptr, out, nullptr, status, iters, kkt);
-}
-extern "C" int cmpc_emu_solve_batch_state(const cmpc_spec *sp, int32_t B, const double *recs, const double *warm,
-                                          const double *state_in, double *out, double *state_out, int32_t *status,
-                                          int32_t *iters, double *kkt) {
-  if (sp->N < 1 || sp->N > CMPC_MAX_N || (sp->nv != 4 && sp->nv != 8)) return 1;
+// What every entry point sets up: the kernel arguments, the slab, the LDS image(s) and the barriers of the workgroup.
+// CMPC_EMU_PAIR=1 runs the 4-vertex solver as the pipelined pair of waves (two LDS images + the exchange words),
+// CMPC_EMU_FAIL_ITER: see above, CMPC_EMU_FILL: what slab, LDS and the gain's saved iterate hold before the first instance.
+struct EmuRun {
   cmpc::KArgs ka;
+  bool pair;
+  double fill;
+  std::vector<double> scratch, lds;
+};
+static bool emu_prepare(EmuRun &r, const cmpc_spec *sp, int32_t B, const double *recs, const double *warm, const double *state_in,
+                        double *out, double *state_out, int32_t *status, int32_t *iters, double *kkt) {
+  if (sp->N < 1 || sp->N > CMPC_MAX_N || (sp->nv != 4 && sp->nv != 8)) return false;
+  cmpc::KArgs &ka = r.ka;
   ka.sp = *sp; ka.B = B; ka.recs = recs; ka.warm = warm; ka.out = out;
   ka.state_in = state_in; ka.state_out = state_out;
   ka.status = status; ka.iters = iters; ka.kkt = kkt; ka.prof = nullptr;
   cmpc::fill_levels(ka);
   // (the 8-vertex solver is a two-wave workgroup: round 5's G'PG keeps one column of the stage block per lane, which one
   // wave of 64 lanes does not have for its 92 columns -- the one-wave form of rounds 2-4 is gone)
-  const int nw8 = cmpc::WAVES_NV8;
   static_assert(cmpc::WAVES_NV8 == 2, "two waves");
   const size_t nd = (sp->nv == 4) ? cmpc::Dims<4>::scratch_doubles(sp->N) : cmpc::Dims<8, 2>::scratch_doubles(sp->N);
-  // CMPC_EMU_PAIR=1 runs the 4-vertex solver as the pipelined pair of waves (two LDS images + the exchange words)
-  const bool pair = sp->nv == 4 && getenv("CMPC_EMU_PAIR") && atoi(getenv("CMPC_EMU_PAIR")) == 1;
-  const size_t nl = pair ? 2 * cmpc::Dims<4, 1, true>::LDS_DOUBLES : (sp->nv == 4) ? cmpc::Dims<4>::LDS_DOUBLES
+  r.pair = sp->nv == 4 && getenv("CMPC_EMU_PAIR") && atoi(getenv("CMPC_EMU_PAIR")) == 1;
+  const size_t nl = r.pair ? 2 * cmpc::Dims<4, 1, true>::LDS_DOUBLES : (sp->nv == 4) ? cmpc::Dims<4>::LDS_DOUBLES
                     : cmpc::Dims<8, 2>::LDS_DOUBLES;
   emu_fail_iter = getenv("CMPC_EMU_FAIL_ITER") ? atoi(getenv("CMPC_EMU_FAIL_ITER")) : -1;
-  const double fill = getenv("CMPC_EMU_FILL") ? atof(getenv("CMPC_EMU_FILL")) : 0.0;
-  std::vector<double> scratch(nd, fill), lds(nl, fill);
-  ka.scratch = scratch.data(); ka.scratch_stride = nd;
+  r.fill = getenv("CMPC_EMU_FILL") ? atof(getenv("CMPC_EMU_FILL")) : 0.0;
+  r.scratch.assign(nd, r.fill); r.lds.assign(nl, r.fill);
+  ka.scratch = r.scratch.data(); ka.scratch_stride = nd;
   emu_barrier.count.store(0); emu_barrier.gen.store(0);
-  emu_barrier.width = ((sp->nv == 8 && nw8 == 2) || pair) ? 128 : 64;
+  emu_barrier.width = (sp->nv == 8 || r.pair) ? 128 : 64;
   for (auto &b : emu_wave_barrier) { b.count.store(0); b.gen.store(0); b.width = 64; }
-  if (pair) run_batch<4, 1, true>(ka, lds.data());
-  else if (sp->nv == 4) run_batch<4, 1>(ka, lds.data());
-  else run_batch<8, 2>(ka, lds.data());
+  return true;
+}
+
+// One launch of the variant <GAIN, CONSTS>: gain [B][CMPC_NGAIN(nv)] / consts [B][CMPC_NCONST], null without the variant.
+template <bool GAIN, bool CONSTS>
+static int emu_solve(const cmpc_spec *sp, int32_t B, const double *recs, const double *warm, const double *state_in, double *out,
+                     double *state_out, int32_t *status, int32_t *iters, double *kkt, double *gain, const double *consts) {
+  EmuRun r;
+  if ((GAIN && !gain) || (CONSTS && !consts) || !emu_prepare(r, sp, B, recs, warm, state_in, out, state_out, status, iters, kkt)) return 1;
+  std::vector<double> gbuf(GAIN ? CMPC_NSTATE(sp->N, sp->nv) : 0, r.fill);
+  if (r.pair) run_batch<4, 1, true, GAIN, CONSTS>(r.ka, r.lds.data(), gain, gbuf.data(), consts);
+  else if (sp->nv == 4) run_batch<4, 1, false, GAIN, CONSTS>(r.ka, r.lds.data(), gain, gbuf.data(), consts);
+  else run_batch<8, 2, false, GAIN, CONSTS>(r.ka, r.lds.data(), gain, gbuf.data(), consts);
   return 0;
+}
+
+extern "C" int cmpc_emu_solve_batch_state(const cmpc_spec *sp, int32_t B, const double *recs, const double *warm,
+                                          const double *state_in, double *out, double *state_out, int32_t *status,
+                                          int32_t *iters, double *kkt) {
+  return emu_solve<false, false>(sp, B, recs, warm, state_in, out, state_out, status, iters, kkt, nullptr, nullptr);
+}
+extern "C" int cmpc_emu_solve_batch(const cmpc_spec *sp, int32_t B, const double *recs, const double *warm,
+                                    double *out, int32_t *status, int32_t *iters, double *kkt) {
+  return cmpc_emu_solve_batch_state(sp, B, recs, warm, nullptr, out, nullptr, status, iters, kkt);
 }
 
 extern "C" int cmpc_emu_lds_bytes(int nv) {
