@@ -229,6 +229,51 @@ int cmpc_tables_set_plan_slots(cmpc_tables *tb, int32_t n_steps, const int32_t *
 int cmpc_build_records_planned(const cmpc_tables *tb, int32_t N, int32_t rate, int32_t B, const int32_t *t,
                                const double *state, const double *plan_pos, double *records, void *stream);
 
+/*
+ * Scene sets: S walks in one cmpc_tables, every instance of a batch names its own by scene_id[b].  All tables are stacked
+ * and padded to T_max rows per scene ([S][T_max][..], host arrays); T[s] <= T_max is the length of scene s, rows beyond it
+ * are never read.  slot_l / slot_r ([S][T_max], entries of a scene's own T[s] rows in [-1, n_steps_max)) may be NULL:
+ * no per-instance plans (then n_steps_max is ignored).  cmpc_tables_create is S = 1; the entry points above serve
+ * S = 1 tables only, the ones below serve any S.
+ */
+int cmpc_scenes_create(int device, int32_t S, int32_t T_max, const int32_t *T, const double *com_tab, const double *pose_l,
+                       const double *pose_r, const double *gl, const double *gr, const double *cur_l, const double *cur_r,
+                       int32_t n_steps_max, const int32_t *slot_l, const int32_t *slot_r, cmpc_tables **out);
+/*
+ * cmpc_build_records_planned with tick t[b] of scene scene_id[b] (int32 [B], device); plan_pos [B][n_steps_max][3] or
+ * NULL.  Checked on the device before any table is read: a record is filled with NaN when scene_id[b] is outside
+ * [0, S), or t[b] < 0, or t[b] + (N+1)*rate >= T[scene_id[b]].  Asynchronous on `stream`, no synchronisation.
+ */
+int cmpc_build_records_scenes(const cmpc_tables *tb, int32_t N, int32_t rate, int32_t B, const int32_t *t,
+                              const int32_t *scene_id, const double *state, const double *plan_pos, double *records,
+                              void *stream);
+/*
+ * Schedule of the contact-plan write-back (code/centroidal_mpc_vertices.py:656-675) for a horizon of N stages `rate`
+ * ticks apart, host arrays [S][T_max]: cond = the write-back may fire at this tick (single support now, double support at
+ * the horizon's end), is_ds = double support, wb_slot = plan entry the landing point goes to (< n_steps_max), wb_row = first
+ * of the three rows of x_N holding it (13: left foot, 17: right foot).  Needs tables with plan slots.
+ */
+int cmpc_scenes_set_schedule(cmpc_tables *tb, int32_t N, int32_t rate, const uint8_t *cond, const uint8_t *is_ds,
+                             const int32_t *wb_slot, const int32_t *wb_row);
+/*
+ * Back half of a closed-loop tick (:614-683) for B instances in one launch, after the solve of records built at tick t[b]
+ * of scene scene_id[b] has returned XU [B][CMPC_NSOL(N, nv)] and status [B].  Per instance, all inputs read first:
+ *   ok = (status is 0 or 3) and alive;
+ *   update_contact != 0:  fire = cond and not flag and ok;  fire -> plan_pos[b][wb_slot] = x_N[wb_row .. wb_row + 2];
+ *                         flag = (flag or fire) and not (is_ds and ok);  counter = fire      (cond, is_ds, .. at (scene, t))
+ *   alive = ok
+ *   ok:  state[0:12] = x_1[0:12];  state[6:9] = hw_next[b] if hw_next;  state[3:6] += push_dv[b] if push_dv;  t += rate;
+ *        warm[b] = XU[b]                                                (copy_all_warm != 0: warm[b] = XU[b] for every b)
+ * Copies and one addition.  alive, flag, counter: one byte per instance, 0 / 1.  An instance whose scene_id is outside
+ * [0, S) or whose t is outside [0, T[scene]) reads no table and counts as not ok.  update_contact != 0 needs
+ * cmpc_scenes_set_schedule with the same N and rate.  hw_next, push_dv [B][3] may be NULL; with update_contact == 0
+ * flag, counter and plan_pos may be.  warm must not overlap XU.  Asynchronous on `stream`, no synchronisation.
+ */
+int cmpc_rollout_advance(const cmpc_tables *tb, int32_t N, int32_t nv, int32_t rate, int32_t B, const int32_t *scene_id,
+                         const double *XU, const int32_t *status, const double *hw_next, const double *push_dv,
+                         int32_t update_contact, int32_t copy_all_warm, int32_t *t, double *state, uint8_t *alive,
+                         uint8_t *flag, uint8_t *counter, double *plan_pos, double *warm, void *stream);
+
 const char *cmpc_last_error(cmpc_handle *h);
 const char *cmpc_version(void);
 

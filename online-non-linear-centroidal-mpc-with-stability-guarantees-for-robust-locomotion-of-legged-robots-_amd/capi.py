@@ -19,7 +19,8 @@ SYMBOLS = ("cmpc_default_spec", "cmpc_create", "cmpc_destroy", "cmpc_workspace_b
            "cmpc_last_kernel_ms", "cmpc_last_kernel_name", "cmpc_last_error",
            "cmpc_version",
            "cmpc_tables_create", "cmpc_tables_destroy", "cmpc_build_records",
-           "cmpc_tables_set_plan_slots", "cmpc_build_records_planned")
+           "cmpc_tables_set_plan_slots", "cmpc_build_records_planned",
+           "cmpc_scenes_create", "cmpc_build_records_scenes", "cmpc_scenes_set_schedule", "cmpc_rollout_advance")
 #: every symbol include/cmpc_wbc.h declares (batched whole-body QP, same library)
 WBC_SYMBOLS = ("cmpc_wbc_qp_solve_batch", "cmpc_wbc_last_error")
 
@@ -71,6 +72,14 @@ def load():
     lib.cmpc_tables_set_plan_slots.restype = ctypes.c_int
     lib.cmpc_build_records_planned.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp]
     lib.cmpc_build_records_planned.restype = ctypes.c_int
+    lib.cmpc_scenes_create.argtypes = [ctypes.c_int, i32, i32, vp] + [vp] * 7 + [i32, vp, vp, ctypes.POINTER(vp)]
+    lib.cmpc_scenes_create.restype = ctypes.c_int
+    lib.cmpc_build_records_scenes.argtypes = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]
+    lib.cmpc_build_records_scenes.restype = ctypes.c_int
+    lib.cmpc_scenes_set_schedule.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    lib.cmpc_scenes_set_schedule.restype = ctypes.c_int
+    lib.cmpc_rollout_advance.argtypes = [vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cmpc_rollout_advance.restype = ctypes.c_int
     f64 = ctypes.c_double
     lib.cmpc_wbc_qp_solve_batch.argtypes = [ctypes.c_int, i32, vp, vp, vp, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, vp]
     lib.cmpc_wbc_qp_solve_batch.restype = ctypes.c_int

@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <string>
+#include <vector>
 
 #include "cmpc_kernel.hpp"
 #include "cmpc_order_fit.h"
@@ -252,15 +253,116 @@ __global__ void __launch_bounds__(256) cmpc_build_records_kernel(
   }
 }
 
+// Scene sets: the tables of S walks stacked [S][T_max][..], instance b reads those of scene_id[b].  Word layout and store
+// pattern of cmpc_build_records_kernel; the scene index is checked first, then the tick against that scene's own length,
+// both before any table is read, so the padding rows behind a scene's T[s] are never touched.
+__global__ void __launch_bounds__(256) cmpc_build_records_scenes_kernel(
+    int S, int T_max, const int *__restrict__ T_tab, int N, int rate, int B, int nrec, const int *__restrict__ tick,
+    const int *__restrict__ scene_id, const double *__restrict__ state, const double *__restrict__ com_tab,
+    const double *__restrict__ pose_l, const double *__restrict__ pose_r, const double *__restrict__ gl,
+    const double *__restrict__ gr, const double *__restrict__ cur_l, const double *__restrict__ cur_r,
+    const double *__restrict__ plan_pos, int n_steps, const int *__restrict__ slot_l_tab, const int *__restrict__ slot_r_tab,
+    double *__restrict__ rec) {
+  const double nanv = __builtin_nan("");
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    const int s = scene_id[b], t = tick[b];
+    bool bad = s < 0 || s >= S;
+    if (!bad) bad = t < 0 || (long long)t + (long long)(N + 1) * rate >= (long long)T_tab[s];
+    const size_t row0 = bad ? 0 : (size_t)s * T_max;       // first row of the instance's scene in every table
+    const double *st16 = state + (size_t)b * 16;
+    const double *plan_b = plan_pos ? plan_pos + (size_t)b * n_steps * 3 : nullptr;
+    const int slot_l = (plan_pos && !bad) ? slot_l_tab[row0 + t] : -1, slot_r = (plan_pos && !bad) ? slot_r_tab[row0 + t] : -1;
+    double *out = rec + (size_t)b * nrec;
+    const bool aligned = ((nrec & 1) == 0);
+    for (int e = 2 * threadIdx.x; e < nrec; e += 2 * blockDim.x) {
+      const double v0 = bad ? nanv : cmpc_record_word(e, t, N, rate, st16, com_tab + row0 * 9, pose_l + row0 * 6, pose_r + row0 * 6,
+                                                      gl + row0, gr + row0, cur_l + row0 * 3, cur_r + row0 * 3, plan_b, slot_l, slot_r);
+      if (e + 1 < nrec) {
+        const double v1 = bad ? nanv : cmpc_record_word(e + 1, t, N, rate, st16, com_tab + row0 * 9, pose_l + row0 * 6, pose_r + row0 * 6,
+                                                        gl + row0, gr + row0, cur_l + row0 * 3, cur_r + row0 * 3, plan_b, slot_l, slot_r);
+        if (aligned) *reinterpret_cast<double2 *>(out + e) = make_double2(v0, v1);
+        else { out[e] = v0; out[e + 1] = v1; }
+      } else out[e] = v0;
+    }
+  }
+}
+
+// Back half of a closed-loop tick (include/cmpc.h, cmpc_rollout_advance): one workgroup per instance, grid-stride.  Every
+// lane reads the instance's few control words (same addresses: one broadcast load each) and its own share of the inputs, the
+// workgroup meets at a barrier, and only then the in-place words (t, alive, flag) are written.  Copies and one addition:
+// nothing here rounds differently from the torch expressions it replaces.  HBM-bound on the XU -> warm copy.
+__global__ void __launch_bounds__(256) cmpc_rollout_advance_kernel(
+    int S, int T_max, const int *__restrict__ T_tab, int N, int nsol, int rate, int B, const int *__restrict__ scene_id,
+    const double *__restrict__ XU, const int *__restrict__ status, const double *__restrict__ hw_next,
+    const double *__restrict__ push_dv, int update_contact, int copy_all_warm, const unsigned char *__restrict__ cond_tab,
+    const unsigned char *__restrict__ is_ds_tab, const int *__restrict__ wb_slot_tab, const int *__restrict__ wb_row_tab,
+    int n_steps, int *tick, double *state, unsigned char *alive, unsigned char *flag, unsigned char *counter,
+    double *plan_pos, double *__restrict__ warm) {
+  const int tid = threadIdx.x;
+  const bool aligned = ((nsol & 1) == 0) && ((((size_t)XU | (size_t)warm) & 15) == 0);   // rows start on 16 bytes
+  for (int b = blockIdx.x; b < B; b += gridDim.x) {
+    const int s = scene_id[b], t = tick[b], st = status[b];
+    bool in_range = s >= 0 && s < S;
+    if (in_range) in_range = t >= 0 && t < T_tab[s];
+    const bool ok = in_range && (st == 0 || st == 3) && alive[b] != 0;
+    const double *xu = XU + (size_t)b * nsol;
+    bool fire = false, new_flag = false;
+    int slot = 0;
+    double land = 0.0, sv = 0.0;
+    if (update_contact) {
+      const bool fl = flag[b] != 0;
+      new_flag = fl;
+      if (in_range) {
+        const size_t k = (size_t)s * T_max + t;
+        fire = cond_tab[k] != 0 && !fl && ok;
+        new_flag = (fl || fire) && !(is_ds_tab[k] != 0 && ok);
+        if (fire) {
+          slot = wb_slot_tab[k];                                         // (slot < n_steps, row 13 or 17: checked on the host
+          if (tid < 3) land = xu[20 * N + wb_row_tab[k] + tid];          //  for every tick of every scene)  x_N[row .. row + 2]
+        }
+      }
+    }
+    if (ok && tid < 12) {
+      sv = xu[20 + tid];                                                 // x_1[0:12]
+      if (hw_next && tid >= 6 && tid < 9) sv = hw_next[(size_t)b * 3 + tid - 6];
+      if (push_dv && tid >= 3 && tid < 6) sv += push_dv[(size_t)b * 3 + tid - 3];
+    }
+    __syncthreads();                                                     // every lane has read t, alive, flag
+    if (tid == 0) {
+      alive[b] = ok ? 1 : 0;
+      if (ok) tick[b] = t + rate;
+      if (update_contact) { flag[b] = new_flag ? 1 : 0; counter[b] = fire ? 1 : 0; }
+    }
+    if (fire && tid < 3) plan_pos[((size_t)b * n_steps + slot) * 3 + tid] = land;
+    if (ok && tid < 12) state[(size_t)b * 16 + tid] = sv;
+    if (ok || copy_all_warm) {
+      double *w = warm + (size_t)b * nsol;
+      if (aligned) {
+        for (int e = 2 * tid; e < nsol; e += 2 * blockDim.x) *reinterpret_cast<double2 *>(w + e) = *reinterpret_cast<const double2 *>(xu + e);
+      } else {
+        for (int e = tid; e < nsol; e += blockDim.x) w[e] = xu[e];
+      }
+    }
+    __syncthreads();                                                     // (grid-stride: the next instance's reads follow these writes)
+  }
+}
+
 }  // namespace
 
 struct cmpc_tables {
   int device = 0;
-  int T = 0;
+  int S = 1;                                        // scenes stacked in every table; the single-scene creators make 1
+  int T = 0;                                        // rows per scene in every table (T_max of a set)
+  std::vector<int> T_host;                          // [S] length of every scene
+  int *T_dev = nullptr;
   double *com_tab = nullptr, *pose_l = nullptr, *pose_r = nullptr, *gl = nullptr, *gr = nullptr,
          *cur_l = nullptr, *cur_r = nullptr;
-  int n_steps = 0;                                  // per-instance plans: entries per plan
-  int *slot_l = nullptr, *slot_r = nullptr;         // [T] plan entry holding the left / right foot of x0, -1 = nominal table
+  int n_steps = 0;                                  // per-instance plans: entries per plan (n_steps_max of a set)
+  int *slot_l = nullptr, *slot_r = nullptr;         // [S][T] plan entry holding the left / right foot of x0, -1 = nominal table
+  // write-back schedule of cmpc_rollout_advance (cmpc_scenes_set_schedule), [S][T], for a horizon of sched_N x sched_rate
+  int sched_N = 0, sched_rate = 0;
+  unsigned char *cond = nullptr, *is_ds = nullptr;
+  int *wb_slot = nullptr, *wb_row = nullptr;
 };
 
 struct cmpc_handle {
@@ -309,6 +411,12 @@ static int fail(cmpc_handle *h, const std::string &msg) {
     hipError_t e_ = (call);                                                                      \
     if (e_ != hipSuccess) return fail(h, std::string(#call) + ": " + hipGetErrorString(e_));     \
   } while (0)
+
+// host array -> device array of the tables (allocated on first use)
+template <class Ty>
+static bool upload(Ty **dst, const Ty *src, size_t n) {
+  return (*dst || hipMalloc(dst, n * sizeof(Ty)) == hipSuccess) && hipMemcpy(*dst, src, n * sizeof(Ty), hipMemcpyHostToDevice) == hipSuccess;
+}
 
 static bool spec_ok(const cmpc_spec *s) {
   return s && s->struct_size == (int32_t)sizeof(cmpc_spec) && s->N >= 1 && s->N <= CMPC_MAX_N &&
@@ -583,6 +691,10 @@ int cmpc_last_kernel_ms(cmpc_handle *h, float *ms) {
   return 0;
 }
 
+static int scenes_create(const char *who, int device, int32_t S, int32_t T_max, const int32_t *T, const double *com_tab,
+                         const double *pose_l, const double *pose_r, const double *gl, const double *gr, const double *cur_l,
+                         const double *cur_r, int32_t n_steps_max, const int32_t *slot_l, const int32_t *slot_r, cmpc_tables **out);
+
 int cmpc_tables_create(int device, int32_t T, const double *com_tab, const double *pose_l, const double *pose_r,
                        const double *gl, const double *gr, const double *cur_l, const double *cur_r,
                        cmpc_tables **out) {
@@ -590,19 +702,53 @@ int cmpc_tables_create(int device, int32_t T, const double *com_tab, const doubl
   *out = nullptr;
   if (T <= 0 || !com_tab || !pose_l || !pose_r || !gl || !gr || !cur_l || !cur_r)
     return fail(nullptr, "cmpc_tables_create: bad argument");
-  DeviceGuard guard(device);
-  if (!guard.ok) return fail(nullptr, "cmpc_tables_create: bad device");
-  cmpc_tables *tb = new cmpc_tables();
-  tb->device = device; tb->T = T;
-  struct { double **dst; const double *src; size_t n; } items[] = {
-      {&tb->com_tab, com_tab, (size_t)T * 9}, {&tb->pose_l, pose_l, (size_t)T * 6}, {&tb->pose_r, pose_r, (size_t)T * 6},
-      {&tb->gl, gl, (size_t)T}, {&tb->gr, gr, (size_t)T}, {&tb->cur_l, cur_l, (size_t)T * 3}, {&tb->cur_r, cur_r, (size_t)T * 3}};
-  for (auto &it : items) {
-    if (hipMalloc(it.dst, it.n * sizeof(double)) != hipSuccess ||
-        hipMemcpy(*it.dst, it.src, it.n * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-      cmpc_tables_destroy(tb);
-      return fail(nullptr, "cmpc_tables_create: device allocation / upload failed");
+  return scenes_create("cmpc_tables_create", device, 1, T, &T, com_tab, pose_l, pose_r, gl, gr, cur_l, cur_r, 0, nullptr, nullptr, out);
+}
+
+int cmpc_scenes_create(int device, int32_t S, int32_t T_max, const int32_t *T, const double *com_tab, const double *pose_l,
+                       const double *pose_r, const double *gl, const double *gr, const double *cur_l, const double *cur_r,
+                       int32_t n_steps_max, const int32_t *slot_l, const int32_t *slot_r, cmpc_tables **out) {
+  return scenes_create("cmpc_scenes_create", device, S, T_max, T, com_tab, pose_l, pose_r, gl, gr, cur_l, cur_r, n_steps_max, slot_l,
+                       slot_r, out);
+}
+
+// who: the entry point the caller used, for the messages
+static int scenes_create(const char *who, int device, int32_t S, int32_t T_max, const int32_t *T, const double *com_tab,
+                         const double *pose_l, const double *pose_r, const double *gl, const double *gr, const double *cur_l,
+                         const double *cur_r, int32_t n_steps_max, const int32_t *slot_l, const int32_t *slot_r, cmpc_tables **out) {
+  const std::string w(who);
+  if (!out) return fail(nullptr, w + ": null out pointer");
+  *out = nullptr;
+  if (S < 1) return fail(nullptr, w + ": S must be at least 1");
+  if (T_max <= 0 || !T) return fail(nullptr, w + ": bad T_max / null T");
+  if (!com_tab || !pose_l || !pose_r || !gl || !gr || !cur_l || !cur_r) return fail(nullptr, w + ": null table");
+  if ((slot_l == nullptr) != (slot_r == nullptr)) return fail(nullptr, w + ": slot_l and slot_r go together");
+  if (slot_l && n_steps_max < 1) return fail(nullptr, w + ": plan slots need n_steps_max >= 1");
+  for (int s = 0; s < S; ++s) {
+    if (T[s] < 1 || T[s] > T_max) return fail(nullptr, w + ": every T[s] must be in [1, T_max]");
+    for (int t = 0; slot_l && t < T[s]; ++t) {
+      const int a = slot_l[(size_t)s * T_max + t], b = slot_r[(size_t)s * T_max + t];
+      if (a < -1 || b < -1 || a >= n_steps_max || b >= n_steps_max) return fail(nullptr, w + ": slot out of range");
     }
+  }
+  DeviceGuard guard(device);
+  if (!guard.ok) return fail(nullptr, w + ": bad device");
+  cmpc_tables *tb = new cmpc_tables();
+  tb->device = device; tb->S = S; tb->T = T_max;
+  tb->T_host.assign(T, T + S);
+  const size_t rows = (size_t)S * T_max;
+  struct { double **dst; const double *src; size_t n; } items[] = {
+      {&tb->com_tab, com_tab, rows * 9}, {&tb->pose_l, pose_l, rows * 6}, {&tb->pose_r, pose_r, rows * 6},
+      {&tb->gl, gl, rows}, {&tb->gr, gr, rows}, {&tb->cur_l, cur_l, rows * 3}, {&tb->cur_r, cur_r, rows * 3}};
+  bool up = upload(&tb->T_dev, T, (size_t)S);
+  for (auto &it : items) up = up && upload(it.dst, it.src, it.n);
+  if (up && slot_l) {
+    up = upload(&tb->slot_l, slot_l, rows) && upload(&tb->slot_r, slot_r, rows);
+    tb->n_steps = n_steps_max;
+  }
+  if (!up) {
+    cmpc_tables_destroy(tb);
+    return fail(nullptr, w + ": device allocation / upload failed");
   }
   *out = tb;
   return 0;
@@ -613,14 +759,15 @@ int cmpc_tables_destroy(cmpc_tables *tb) {
   DeviceGuard guard(tb->device);
   double *ptrs[] = {tb->com_tab, tb->pose_l, tb->pose_r, tb->gl, tb->gr, tb->cur_l, tb->cur_r};
   for (double *p : ptrs) if (p) (void)hipFree(p);
-  if (tb->slot_l) (void)hipFree(tb->slot_l);
-  if (tb->slot_r) (void)hipFree(tb->slot_r);
+  void *more[] = {tb->T_dev, tb->slot_l, tb->slot_r, tb->cond, tb->is_ds, tb->wb_slot, tb->wb_row};
+  for (void *p : more) if (p) (void)hipFree(p);
   delete tb;
   return 0;
 }
 
 int cmpc_tables_set_plan_slots(cmpc_tables *tb, int32_t n_steps, const int32_t *slot_l, const int32_t *slot_r) {
   if (!tb || n_steps < 1 || !slot_l || !slot_r) return fail(nullptr, "cmpc_tables_set_plan_slots: bad argument");
+  if (tb->S != 1) return fail(nullptr, "cmpc_tables_set_plan_slots: a scene set takes its slots at cmpc_scenes_create");
   for (int t = 0; t < tb->T; ++t)
     if (slot_l[t] >= n_steps || slot_r[t] >= n_steps) return fail(nullptr, "cmpc_tables_set_plan_slots: slot out of range");
   DeviceGuard guard(tb->device);
@@ -642,6 +789,7 @@ int cmpc_build_records(const cmpc_tables *tb, int32_t N, int32_t rate, int32_t B
 int cmpc_build_records_planned(const cmpc_tables *tb, int32_t N, int32_t rate, int32_t B, const int32_t *t,
                                const double *state, const double *plan_pos, double *records, void *stream) {
   if (!tb) return fail(nullptr, "cmpc_build_records: null tables");
+  if (tb->S != 1) return fail(nullptr, "cmpc_build_records: the tables hold several scenes (cmpc_build_records_scenes takes a scene index)");
   if (plan_pos && (!tb->slot_l || tb->n_steps < 1)) return fail(nullptr, "cmpc_build_records_planned: call cmpc_tables_set_plan_slots first");
   if (N < 1 || N > CMPC_MAX_N || rate < 1 || B < 0) return fail(nullptr, "cmpc_build_records: bad argument");
   if (B == 0) return 0;
@@ -654,6 +802,75 @@ int cmpc_build_records_planned(const cmpc_tables *tb, int32_t N, int32_t rate, i
                      B, nrec, t, state, tb->com_tab, tb->pose_l, tb->pose_r, tb->gl, tb->gr, tb->cur_l, tb->cur_r,
                      plan_pos, tb->n_steps, tb->slot_l, tb->slot_r, records);
   if (hipGetLastError() != hipSuccess) return fail(nullptr, "cmpc_build_records: launch failed");
+  return 0;
+}
+
+int cmpc_build_records_scenes(const cmpc_tables *tb, int32_t N, int32_t rate, int32_t B, const int32_t *t,
+                              const int32_t *scene_id, const double *state, const double *plan_pos, double *records,
+                              void *stream) {
+  if (!tb) return fail(nullptr, "cmpc_build_records_scenes: null tables");
+  if (plan_pos && (!tb->slot_l || tb->n_steps < 1)) return fail(nullptr, "cmpc_build_records_scenes: the tables were created without plan slots");
+  if (N < 1 || N > CMPC_MAX_N || rate < 1 || B < 0) return fail(nullptr, "cmpc_build_records_scenes: bad argument");
+  if (B == 0) return 0;
+  if (!t || !scene_id || !state || !records) return fail(nullptr, "cmpc_build_records_scenes: null buffer");
+  DeviceGuard guard(tb->device);
+  if (!guard.ok) return fail(nullptr, "cmpc_build_records_scenes: bad device");
+  const int nrec = CMPC_NREC(N);
+  const int blocks = B < 256 * 32 ? B : 256 * 32;
+  hipLaunchKernelGGL(cmpc_build_records_scenes_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, tb->S, tb->T,
+                     tb->T_dev, N, rate, B, nrec, t, scene_id, state, tb->com_tab, tb->pose_l, tb->pose_r, tb->gl, tb->gr,
+                     tb->cur_l, tb->cur_r, plan_pos, tb->n_steps, tb->slot_l, tb->slot_r, records);
+  if (hipGetLastError() != hipSuccess) return fail(nullptr, "cmpc_build_records_scenes: launch failed");
+  return 0;
+}
+
+int cmpc_scenes_set_schedule(cmpc_tables *tb, int32_t N, int32_t rate, const uint8_t *cond, const uint8_t *is_ds,
+                             const int32_t *wb_slot, const int32_t *wb_row) {
+  if (!tb) return fail(nullptr, "cmpc_scenes_set_schedule: null tables");
+  if (N < 1 || N > CMPC_MAX_N || rate < 1) return fail(nullptr, "cmpc_scenes_set_schedule: bad argument");
+  if (!cond || !is_ds || !wb_slot || !wb_row) return fail(nullptr, "cmpc_scenes_set_schedule: null buffer");
+  if (!tb->slot_l || tb->n_steps < 1) return fail(nullptr, "cmpc_scenes_set_schedule: the tables were created without plan slots");
+  for (int s = 0; s < tb->S; ++s)
+    for (int t = 0; t < tb->T_host[s]; ++t) {
+      const size_t k = (size_t)s * tb->T + t;
+      if (wb_slot[k] < 0 || wb_slot[k] >= tb->n_steps) return fail(nullptr, "cmpc_scenes_set_schedule: wb_slot out of range");
+      if (wb_row[k] != 13 && wb_row[k] != 17) return fail(nullptr, "cmpc_scenes_set_schedule: wb_row must be 13 or 17");
+    }
+  DeviceGuard guard(tb->device);
+  if (!guard.ok) return fail(nullptr, "cmpc_scenes_set_schedule: bad device");
+  const size_t rows = (size_t)tb->S * tb->T;
+  tb->sched_N = tb->sched_rate = 0;
+  if (!upload(&tb->cond, cond, rows) || !upload(&tb->is_ds, is_ds, rows) || !upload(&tb->wb_slot, wb_slot, rows) ||
+      !upload(&tb->wb_row, wb_row, rows))
+    return fail(nullptr, "cmpc_scenes_set_schedule: device allocation / upload failed");
+  tb->sched_N = N; tb->sched_rate = rate;
+  return 0;
+}
+
+int cmpc_rollout_advance(const cmpc_tables *tb, int32_t N, int32_t nv, int32_t rate, int32_t B, const int32_t *scene_id,
+                         const double *XU, const int32_t *status, const double *hw_next, const double *push_dv,
+                         int32_t update_contact, int32_t copy_all_warm, int32_t *t, double *state, uint8_t *alive,
+                         uint8_t *flag, uint8_t *counter, double *plan_pos, double *warm, void *stream) {
+  if (!tb) return fail(nullptr, "cmpc_rollout_advance: null tables");
+  if (N < 1 || N > CMPC_MAX_N || (nv != 4 && nv != 8) || rate < 1 || B < 0) return fail(nullptr, "cmpc_rollout_advance: bad argument");
+  if (update_contact && (!tb->cond || tb->sched_N != N || tb->sched_rate != rate))
+    return fail(nullptr, "cmpc_rollout_advance: no write-back schedule for this N and rate (cmpc_scenes_set_schedule)");
+  if (B == 0) return 0;
+  if (!scene_id || !XU || !status || !t || !state || !alive || !warm) return fail(nullptr, "cmpc_rollout_advance: null buffer");
+  if (update_contact && (!flag || !counter || !plan_pos)) return fail(nullptr, "cmpc_rollout_advance: null flag / counter / plan_pos");
+  const int nsol = CMPC_NSOL(N, nv);
+  {
+    const char *a = (const char *)XU, *b = (const char *)warm;
+    const size_t nb = (size_t)B * nsol * sizeof(double);
+    if (a < b + nb && b < a + nb) return fail(nullptr, "cmpc_rollout_advance: warm overlaps XU");
+  }
+  DeviceGuard guard(tb->device);
+  if (!guard.ok) return fail(nullptr, "cmpc_rollout_advance: bad device");
+  const int blocks = B < 256 * 32 ? B : 256 * 32;
+  hipLaunchKernelGGL(cmpc_rollout_advance_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, tb->S, tb->T, tb->T_dev,
+                     N, nsol, rate, B, scene_id, XU, status, hw_next, push_dv, update_contact ? 1 : 0, copy_all_warm ? 1 : 0,
+                     tb->cond, tb->is_ds, tb->wb_slot, tb->wb_row, tb->n_steps, t, state, alive, flag, counter, plan_pos, warm);
+  if (hipGetLastError() != hipSuccess) return fail(nullptr, "cmpc_rollout_advance: launch failed");
   return 0;
 }
 

@@ -17,21 +17,58 @@ twin of this loop is ``walk.WalkHarness`` around the drop-in class):
      whole tick -- records, MPC solve, write-back, QP -- stays on the device.
 Everything after the solve is index arithmetic and copies in torch (device memory plumbing); the schedule
 (phases, step indices) is shared by the batch, the plan positions are per instance.
+
+A fleet: with a ``workloads.SceneSet`` every instance walks the command of its own scene (``scene_id``): the records come
+from ``cmpc_build_records_scenes`` and step 3 is one launch, ``cmpc_rollout_advance``, indexed by (scene, tick); only the
+momentum lookup stays a torch gather.  With ``consts`` every instance is solved with its own 18 problem constants
+(``solve_with_consts``), with one scene or with a set.
 """
 import numpy as np
 import torch
 
+from .problem import CONST_FIELDS, NCONST
 from .solver import BatchedCentroidalMPC, DeviceRecordBuilder, usable
+from .workloads import SceneSet, rollout_schedule
+
+
+def _checked_consts(consts, spec, B):
+    """(B, 18) host copy of the per-instance constants, refused unless every row steps by the spec's delta: the schedule
+    advances by `rate` ticks for the whole batch."""
+    c = consts.detach().cpu().numpy() if isinstance(consts, torch.Tensor) else np.asarray(consts)
+    c = np.ascontiguousarray(c, dtype=np.float64)
+    if c.shape != (B, NCONST):
+        raise ValueError(f"consts must have shape (B, {NCONST}) = ({B}, {NCONST})")
+    bad = np.nonzero(c[:, CONST_FIELDS.index("delta")] != spec.delta)[0]
+    if bad.size:
+        raise ValueError(f"consts rows {bad[:8].tolist()} have a delta other than the spec's {spec.delta}: one batch "
+                         f"advances by one tick length")
+    return c
 
 
 class BatchedRollout:
     def __init__(self, scene, spec, B, device="cuda:0", mass=None, mu=0.5, update_contact=True,
-                 hw_measured=None, hw_offset=None, rate=1):
+                 hw_measured=None, hw_offset=None, rate=1, scene_id=None, consts=None):
+        """scene: a ``workloads.Scene`` (one walk for the batch) or a ``workloads.SceneSet`` with ``scene_id`` (B,) naming
+        every instance's walk (optional for a set of one).  hw_measured: one recording (ticks, 3), or with a set one per
+        scene.  consts (B, 18): per-instance problem constants, every row with the spec's delta."""
+        consts = None if consts is None else _checked_consts(consts, spec, B)
+        self._set = scene if isinstance(scene, SceneSet) else None
+        if self._set is None and scene_id is not None:
+            raise ValueError("scene_id goes with a SceneSet")
+        if self._set is not None:
+            if scene_id is None and scene.S > 1:
+                raise ValueError("a SceneSet of several scenes needs scene_id")
+            sid = np.zeros(B, np.int32) if scene_id is None else np.asarray(
+                scene_id.cpu() if isinstance(scene_id, torch.Tensor) else scene_id)
+            if sid.shape != (B,) or (sid < 0).any() or (sid >= scene.S).any():
+                raise ValueError(f"scene_id must hold B indices in [0, {scene.S})")
+            sid = sid.astype(np.int32)
         self.scene, self.spec, self.B, self.rate = scene, spec, B, rate
         self.solver = BatchedCentroidalMPC(spec, device=device)
         self.device = self.solver.device
         self.builder = DeviceRecordBuilder(scene, device=self.device)
         dev, f64 = self.device, torch.float64
+        self.consts = None if consts is None else torch.from_numpy(consts).to(dev)
         self.state = torch.zeros((B, 16), dtype=f64, device=dev)
         self.state[:, 14] = scene.params['mass'] if mass is None else torch.as_tensor(mass, dtype=f64, device=dev)
         self.state[:, 15] = torch.as_tensor(mu, dtype=f64, device=dev)
@@ -42,22 +79,46 @@ class BatchedRollout:
         self.alive = torch.ones(B, dtype=torch.bool, device=dev)
         # per-instance plans and the shared schedule (:656-675)
         self.update_contact = update_contact
-        self.plan_pos = torch.from_numpy(scene.plan_pos).to(dev).repeat(B, 1, 1).contiguous()
         self.flag = torch.zeros(B, dtype=torch.bool, device=dev)             # update_contact_flag
         self.counter = torch.zeros(B, dtype=torch.bool, device=dev)          # model_state['counter'] of the last tick
-        T, N = scene.T, spec.N
-        end = np.minimum(np.arange(T) + N * rate - 1, T - 1)
-        cond = scene.is_ss & ~scene.is_ss[end]                                # now 'ss', horizon end 'ds'
-        self._cond = torch.from_numpy(cond).to(dev)
-        self._is_ds = torch.from_numpy(~scene.is_ss).to(dev)
-        self._wb_slot = torch.from_numpy(np.minimum(scene.step_idx + 1, scene.plan_pos.shape[0] - 1).astype(np.int64)).to(dev)
-        # support = lfoot -> the swing foot is the right one -> rows 17:20 of x_N, else rows 13:16
-        self._wb_row = torch.from_numpy(np.where(scene.support_is_l, 17, 13).astype(np.int64)).to(dev)
-        self.hw_measured = None if hw_measured is None else torch.as_tensor(np.asarray(hw_measured), dtype=f64, device=dev)
         self.hw_offset = None if hw_offset is None else torch.as_tensor(np.asarray(hw_offset), dtype=f64, device=dev)
         self._gl = torch.from_numpy(np.ascontiguousarray(scene.gl_tab)).to(dev)
         self._gr = torch.from_numpy(np.ascontiguousarray(scene.gr_tab)).to(dev)
         self._wbc = None
+        if self._set is not None:
+            self._init_set(sid, hw_measured)
+            return
+        self.plan_pos = torch.from_numpy(scene.plan_pos).to(dev).repeat(B, 1, 1).contiguous()
+        cond, is_ds, wb_slot, wb_row = rollout_schedule(scene, spec.N, rate)
+        self._cond = torch.from_numpy(cond).to(dev)
+        self._is_ds = torch.from_numpy(is_ds).to(dev)
+        self._wb_slot = torch.from_numpy(wb_slot).to(dev)
+        self._wb_row = torch.from_numpy(wb_row).to(dev)
+        self.hw_measured = None if hw_measured is None else torch.as_tensor(np.asarray(hw_measured), dtype=f64, device=dev)
+
+    def _init_set(self, sid, hw_measured):
+        """The per-instance side of a scene set: scene indices, plans (padded to n_steps_max) and momentum recordings."""
+        sset, dev, f64 = self._set, self.device, torch.float64
+        self.scene_id = torch.from_numpy(sid).to(dev)
+        self._sid = self.scene_id.long()
+        self._t_last = torch.from_numpy(sset.T.astype(np.int64) - 1).to(dev)[self._sid]      # last tick of the instance's scene
+        self.plan_pos = torch.from_numpy(sset.plan_pos).to(dev)[self._sid].contiguous()
+        self._warm_buf = torch.empty((self.B, self.spec.nsol), dtype=f64, device=dev)
+        if self.update_contact:
+            self.builder.set_schedule(sset, self.spec.N, self.rate)
+        # one recording for every scene, or one per scene (rows of different length padded with NaN, never read)
+        self.hw_measured = None
+        if hw_measured is not None:
+            one = not isinstance(hw_measured, (list, tuple))
+            recs = [np.asarray(h, dtype=np.float64) for h in ([hw_measured] if one else hw_measured)]
+            if not one and len(recs) != sset.S:
+                raise ValueError(f"hw_measured: one recording, or a list of one per scene ({sset.S})")
+            pad = np.full((len(recs), max(len(h) for h in recs), 3), np.nan)
+            for i, h in enumerate(recs):
+                pad[i, :len(h)] = h
+            self.hw_measured = torch.from_numpy(pad).to(dev)
+            self._hw_sid = torch.zeros(self.B, dtype=torch.int64, device=dev) if one else self._sid
+            self._hw_last = torch.tensor([len(h) - 1 for h in recs], dtype=torch.int64, device=dev)[self._hw_sid]
 
     def attach_whole_body(self, qp, model):
         """Run the whole-body QP inside every tick.  ``qp``: a ``wbc.BatchedInverseDynamicsQP``; ``model(rollout, desired)``
@@ -72,14 +133,21 @@ class BatchedRollout:
         """``model_state['com']`` of the reference's back half (:633-649) for the batch: position and velocity of x_1 and
         CoM_acc = (gamma_l sum F_l + gamma_r sum F_r) / m + (0, 0, -g) from u_0 and the contact flags at tick t."""
         nv = self.spec.nv
-        tl = torch.clamp(t.long(), max=self._gl.shape[0] - 1)
-        gl, gr = self._gl[tl], self._gr[tl]
+        if self._set is None:
+            tl = torch.clamp(t.long(), max=self._gl.shape[0] - 1)
+            gl, gr = self._gl[tl], self._gr[tl]
+        else:                                                                 # the flags of the instance's own scene
+            tl = torch.minimum(t.long(), self._t_last)
+            gl, gr = self._gl[self._sid, tl], self._gr[self._sid, tl]
         F = u0[:, :6 * nv].reshape(-1, 2, nv, 3).sum(dim=2)                  # (B, foot, 3)
         acc = (gl[:, None] * F[:, 0] + gr[:, None] * F[:, 1]) / self.state[:, 14:15]
         acc = acc + torch.tensor([0.0, 0.0, -self.spec.g], dtype=torch.float64, device=self.device)
         return {"com_pos": x1[:, 0:3], "com_vel": x1[:, 3:6], "com_acc": acc, "gamma_l": gl, "gamma_r": gr}
 
     def _hw_at(self, t):
+        if self._set is not None:
+            h = self.hw_measured[self._hw_sid, torch.minimum(t.long(), self._hw_last)]
+            return h if self.hw_offset is None else h + self.hw_offset
         h = self.hw_measured[torch.clamp(t.long(), max=self.hw_measured.shape[0] - 1)]
         return h if self.hw_offset is None else h + self.hw_offset
 
@@ -100,15 +168,48 @@ class BatchedRollout:
         self._state[0].zero_()
         self.alive[:] = True
         self.flag[:] = False
-        self.plan_pos = torch.from_numpy(self.scene.plan_pos).to(dev).repeat(self.B, 1, 1).contiguous()
+        if self._set is not None:
+            self.plan_pos = torch.from_numpy(self._set.plan_pos).to(dev)[self._sid].contiguous()
+        else:
+            self.plan_pos = torch.from_numpy(self.scene.plan_pos).to(dev).repeat(self.B, 1, 1).contiguous()
+
+    def _solve_tick(self, rec, s_in, s_out):
+        if self.consts is not None:
+            return self.solver.solve_with_consts(rec, self.consts, warm=self.warm, state=s_in, state_out=s_out)
+        return self.solver.solve(rec, warm=self.warm, state=s_in, state_out=s_out)
+
+    def _step_set(self, push_dv):
+        """``step`` of a fleet: records by (scene, tick), the solve, then the back half in one launch."""
+        sp, N, dev = self.spec, self.spec.N, self.device
+        rec = self.builder.build(sp, self.t, self.state, rate=self.rate, scene_id=self.scene_id,
+                                 plan_pos=self.plan_pos if self.update_contact else None)
+        s_in, s_out = self._state
+        XU, status, iters, kkt = self._solve_tick(rec, s_in, s_out)
+        self._state = [s_out, s_in]
+        x1 = XU[:, 20:40]
+        u0 = XU[:, 20 * (N + 1):20 * (N + 1) + sp.nu]
+        self.last_records, self.last_XU, self.last_status, self.last_iters = rec, XU, status, iters
+        if self._wbc is not None:
+            qp, model = self._wbc
+            self.last_wbc = qp.solve(*model(self, self.desired_com(x1, u0, self.t)))
+        hw_next = None if self.hw_measured is None else self._hw_at(self.t + self.rate)
+        if push_dv is not None:
+            push_dv = torch.as_tensor(push_dv, dtype=torch.float64, device=dev).expand(self.B, 3).contiguous()
+        self.builder.advance(sp, self.rate, self.scene_id, XU, status, self.t, self.state, self.alive, self._warm_buf,
+                             flag=self.flag, counter=self.counter, plan_pos=self.plan_pos, hw_next=hw_next, push_dv=push_dv,
+                             update_contact=self.update_contact, copy_all_warm=self.warm is None)
+        self.warm = self._warm_buf
+        return x1, u0, status
 
     def step(self, push_dv=None):
         """One control tick for every instance.  Returns (x1 (B,20), u0 (B,nu), status (B,))."""
+        if self._set is not None:
+            return self._step_set(push_dv)
         sp, N = self.spec, self.spec.N
         rec = self.builder.build(sp, self.t, self.state, rate=self.rate,
                                  plan_pos=self.plan_pos if self.update_contact else None)
         s_in, s_out = self._state
-        XU, status, iters, kkt = self.solver.solve(rec, warm=self.warm, state=s_in, state_out=s_out)
+        XU, status, iters, kkt = self._solve_tick(rec, s_in, s_out)
         ok = usable(status) & self.alive
         self._state = [s_out, s_in]              # (an instance whose solve failed stops for good, see `alive`)
         x1 = XU[:, 20:40]

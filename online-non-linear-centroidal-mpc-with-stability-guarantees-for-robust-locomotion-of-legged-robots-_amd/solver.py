@@ -173,7 +173,9 @@ class BatchedCentroidalMPC:
 class DeviceRecordBuilder:
     """Device-side front half of ``centroidal_mpc.solve`` (code/centroidal_mpc_vertices.py:482-600): the
     per-tick tables of a ``workloads.Scene`` are uploaded once, then records for a whole batch are
-    gathered on the GPU (``cmpc_build_records``) - no host loop, no host-to-device copy per tick."""
+    gathered on the GPU (``cmpc_build_records``) - no host loop, no host-to-device copy per tick.
+    With a ``workloads.SceneSet`` the tables of all its walks are uploaded and every instance names its own by
+    ``scene_id`` (``cmpc_build_records_scenes``)."""
 
     def __init__(self, scene, device=None):
         import numpy as np
@@ -181,6 +183,10 @@ class DeviceRecordBuilder:
             raise RuntimeError("DeviceRecordBuilder needs a ROCm GPU: there is no CPU fallback")
         self.device = _device_of(device)
         self._lib = capi.load()
+        self.S = getattr(scene, "S", None)     # a workloads.SceneSet has S scenes; None: one Scene, today's entry points
+        if self.S is not None:
+            self._init_set(scene)
+            return
         T = scene.T
         arrs = [np.ascontiguousarray(a[:T], dtype=np.float64) for a in
                 (scene.com_tab, scene.pose_l, scene.pose_r, scene.gl_tab, scene.gr_tab, scene.cur_l, scene.cur_r)]
@@ -197,6 +203,69 @@ class DeviceRecordBuilder:
         if rc != 0:
             raise RuntimeError("cmpc_tables_set_plan_slots failed: " + self._lib.cmpc_last_error(None).decode())
 
+    def _init_set(self, sset):
+        import numpy as np
+        p = lambda a: a.ctypes.data_as(ctypes.c_void_p)
+        T = np.ascontiguousarray(sset.T, dtype=np.int32)
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in
+                (sset.com_tab, sset.pose_l, sset.pose_r, sset.gl_tab, sset.gr_tab, sset.cur_l, sset.cur_r)]
+        sl, sr = (np.ascontiguousarray(a, dtype=np.int32) for a in (sset.slot_l, sset.slot_r))
+        h = ctypes.c_void_p()
+        rc = self._lib.cmpc_scenes_create(self.device.index, sset.S, sset.T_max, p(T), *[p(a) for a in arrs],
+                                          sset.n_steps_max, p(sl), p(sr), ctypes.byref(h))
+        if rc != 0:
+            raise RuntimeError("cmpc_scenes_create failed: " + self._lib.cmpc_last_error(None).decode())
+        self._h, self.T, self.n_steps = h, T.copy(), int(sset.n_steps_max)
+
+    def set_schedule(self, sset, N, rate=1):
+        """Upload ``sset.schedule(N, rate)``, the write-back tables ``advance`` reads (``cmpc_scenes_set_schedule``)."""
+        import numpy as np
+        cond, is_ds, wb_slot, wb_row = sset.schedule(N, rate)
+        arrs = [np.ascontiguousarray(cond, dtype=np.uint8), np.ascontiguousarray(is_ds, dtype=np.uint8),
+                np.ascontiguousarray(wb_slot, dtype=np.int32), np.ascontiguousarray(wb_row, dtype=np.int32)]
+        rc = self._lib.cmpc_scenes_set_schedule(self._h, N, rate, *[a.ctypes.data_as(ctypes.c_void_p) for a in arrs])
+        if rc != 0:
+            raise RuntimeError("cmpc_scenes_set_schedule failed: " + self._lib.cmpc_last_error(None).decode())
+
+    def _check_scene_id(self, scene_id, B):
+        if self.S is None:
+            raise ValueError("scene_id goes with a SceneSet: this builder holds one Scene")
+        if not (isinstance(scene_id, torch.Tensor) and scene_id.is_cuda and scene_id.dtype == torch.int32
+                and scene_id.is_contiguous() and tuple(scene_id.shape) == (B,) and scene_id.device == self.device):
+            raise ValueError(f"scene_id must be a contiguous int32 CUDA tensor of shape (B,) on {self.device}")
+
+    def advance(self, spec, rate, scene_id, XU, status, t, state, alive, warm, flag=None, counter=None, plan_pos=None,
+                hw_next=None, push_dv=None, update_contact=True, copy_all_warm=False):
+        """Back half of a closed-loop tick in one launch (``cmpc_rollout_advance``, include/cmpc.h): t, state, alive, flag,
+        counter, plan_pos and warm are updated in place from the solve's XU and status; flag, counter and plan_pos go with
+        update_contact and are left alone (and may be None) without it.  Scene sets only."""
+        B = t.shape[0]
+        self._check_scene_id(scene_id, B)
+        f64, dev = torch.float64, self.device
+
+        def ok(x, dtype, shape):
+            return x.is_cuda and x.dtype == dtype and x.is_contiguous() and tuple(x.shape) == shape and x.device == dev
+        if not (ok(XU, f64, (B, spec.nsol)) and ok(warm, f64, (B, spec.nsol)) and ok(status, torch.int32, (B,))
+                and ok(t, torch.int32, (B,)) and ok(state, f64, (B, 16)) and ok(alive, torch.bool, (B,))):
+            raise ValueError(f"advance: every buffer must be a contiguous tensor of its documented shape and type on {dev}")
+        if update_contact and not (ok(flag, torch.bool, (B,)) and ok(counter, torch.bool, (B,))
+                                   and ok(plan_pos, f64, (B, self.n_steps, 3))):
+            raise ValueError(f"advance: flag, counter (B,) bool and plan_pos (B, {self.n_steps}, 3) fp64 go with update_contact")
+        if not update_contact:                                   # the kernel touches none of the three
+            flag = counter = plan_pos = None
+        for x in (hw_next, push_dv):
+            if x is not None and not ok(x, f64, (B, 3)):
+                raise ValueError("advance: hw_next / push_dv must be contiguous fp64 CUDA tensors of shape (B, 3)")
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        rc = self._lib.cmpc_rollout_advance(self._h, spec.N, spec.nv, rate, B, scene_id.data_ptr(), XU.data_ptr(), status.data_ptr(),
+                                            hw_next.data_ptr() if hw_next is not None else None,
+                                            push_dv.data_ptr() if push_dv is not None else None,
+                                            int(bool(update_contact)), int(bool(copy_all_warm)), t.data_ptr(), state.data_ptr(),
+                                            alive.data_ptr(), *[x.data_ptr() if x is not None else None for x in (flag, counter, plan_pos)],
+                                            warm.data_ptr(), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("cmpc_rollout_advance failed: " + self._lib.cmpc_last_error(None).decode())
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.cmpc_tables_destroy(self._h)
@@ -208,9 +277,11 @@ class DeviceRecordBuilder:
         except Exception:
             pass
 
-    def build(self, spec, t, state, rate=1, out=None, plan_pos=None):
+    def build(self, spec, t, state, rate=1, out=None, plan_pos=None, scene_id=None):
         """t (B,) int32 and state (B, 16) fp64 on the GPU -> records (B, nrec) on the GPU.  plan_pos
-        (B, n_steps, 3): per-instance contact plans (the x0 foot positions of :493-509 come from them)."""
+        (B, n_steps, 3): per-instance contact plans (the x0 foot positions of :493-509 come from them).
+        scene_id (B,) int32 on the GPU: the walk of every instance -- required with a ``SceneSet`` (n_steps is then
+        its n_steps_max), refused with one ``Scene``.  A scene index or tick outside its range gives a NaN record."""
         if not (t.is_cuda and t.dtype == torch.int32 and t.is_contiguous()):
             raise ValueError("t must be a contiguous int32 CUDA tensor")
         if t.device != self.device or state.device != self.device:
@@ -225,6 +296,16 @@ class DeviceRecordBuilder:
                                          and tuple(plan_pos.shape) == (B, self.n_steps, 3) and plan_pos.device == self.device):
             raise ValueError(f"plan_pos must be a contiguous fp64 tensor of shape (B, {self.n_steps}, 3) on {self.device}")
         stream = torch.cuda.current_stream(t.device).cuda_stream
+        if self.S is not None or scene_id is not None:
+            if scene_id is None:
+                raise ValueError("this builder holds a SceneSet: build() needs scene_id")
+            self._check_scene_id(scene_id, B)
+            rc = self._lib.cmpc_build_records_scenes(self._h, spec.N, rate, B, t.data_ptr(), scene_id.data_ptr(), state.data_ptr(),
+                                                     plan_pos.data_ptr() if plan_pos is not None else None,
+                                                     out.data_ptr(), ctypes.c_void_p(stream))
+            if rc != 0:
+                raise RuntimeError("cmpc_build_records_scenes failed: " + self._lib.cmpc_last_error(None).decode())
+            return out
         rc = self._lib.cmpc_build_records_planned(self._h, spec.N, rate, B, t.data_ptr(), state.data_ptr(),
                                                   plan_pos.data_ptr() if plan_pos is not None else None,
                                                   out.data_ptr(), ctypes.c_void_p(stream))

@@ -36,14 +36,16 @@ def default_params(N=10, mpc_rate=1):
 
 
 class Scene:
-    """Planner + references of the shipped walk and per-tick gather tables."""
+    """Planner + references of one walk and per-tick gather tables.  vref: the velocity commands handed to
+    ``FootstepPlanner`` (None = the shipped walk ``VREF``); ``params['first_swing']`` names the foot that swings first."""
 
-    def __init__(self, params=None):
+    def __init__(self, params=None, vref=None):
         self.params = default_params() if params is None else params
+        self.vref = VREF if vref is None else list(vref)
         self.initial = {'lfoot': {'pos': LFOOT0.copy()}, 'rfoot': {'pos': RFOOT0.copy()},
                         'com': {'pos': np.array([0., 0., 0.72]), 'vel': np.zeros(3)},
                         'hw': {'val': np.zeros(3)}}
-        self.planner = FootstepPlanner(VREF, LFOOT0, RFOOT0, self.params)
+        self.planner = FootstepPlanner(self.vref, LFOOT0, RFOOT0, self.params)
         self.ftg = FootTrajectoryGenerator(self.initial, self.planner, self.params)
         self.com_ref = references(self.ftg, self.planner)
         self.refresh_tables()
@@ -112,6 +114,108 @@ class Scene:
         t = np.asarray(t, dtype=np.int64)
         com = np.stack([self.com_tab[t, 0], self.com_tab[t, 1], np.full(t.shape, 0.72)], axis=1)
         dcom = np.stack([self.com_tab[t, 3], self.com_tab[t, 4], np.zeros(t.shape)], axis=1)
+        return com, dcom
+
+
+def rollout_schedule(sc, N, rate=1):
+    """Per-tick tables of the contact-plan write-back (code/centroidal_mpc_vertices.py:656-675) for one ``Scene`` and a
+    horizon of N stages `rate` ticks apart, T entries each:
+      cond     now single support, horizon end double support: the write-back may fire
+      is_ds    double support: the update flag is cleared
+      wb_slot  plan entry the landing point goes to (the step after the current one)
+      wb_row   rows of x_N holding it: support = lfoot -> the swing foot is the right one -> 17:20, else 13:16"""
+    T = sc.T
+    end = np.minimum(np.arange(T) + N * rate - 1, T - 1)
+    cond = sc.is_ss & ~sc.is_ss[end]
+    wb_slot = np.minimum(sc.step_idx + 1, sc.plan_pos.shape[0] - 1).astype(np.int64)
+    wb_row = np.where(sc.support_is_l, 17, 13).astype(np.int64)
+    return cond, ~sc.is_ss, wb_slot, wb_row
+
+
+class SceneSet:
+    """S walks with their per-tick tables stacked: ``com_tab`` (S, T_max, 9), ``pose_l`` / ``pose_r`` (S, T_max, 6),
+    ``gl_tab`` / ``gr_tab`` (S, T_max), ``cur_l`` / ``cur_r`` (S, T_max, 3), ``slot_l`` / ``slot_r`` (S, T_max),
+    ``plan_pos`` (S, n_steps_max, 3), ``is_ss`` / ``step_idx`` / ``support_is_l`` (S, T_max).  Every instance of a batch
+    names its walk by a scene index.  Rows beyond a scene's own ``T[s]`` / ``n_steps[s]`` are padding: NaN for doubles,
+    -1 for slots and step indices, False for flags -- a read of padding shows.  The scenes may differ in the velocity
+    commands, ``first_swing`` and the phase durations; the tick length, the default mass and ``mpc_rate`` are shared
+    (one batch advances by one ``rate``)."""
+
+    SHARED = ('world_time_step', 'mass', 'mpc_rate')
+
+    def __init__(self, scenes):
+        scenes = list(scenes)
+        if not scenes:
+            raise ValueError("a SceneSet needs at least one Scene")
+        for k in self.SHARED:
+            if any(sc.params[k] != scenes[0].params[k] for sc in scenes):
+                raise ValueError(f"all scenes of a set must share params[{k!r}]")
+        self.scenes, self.params = scenes, scenes[0].params
+        self.S = S = len(scenes)
+        self.T = np.array([sc.T for sc in scenes], dtype=np.int32)
+        self.n_steps = np.array([sc.plan_pos.shape[0] for sc in scenes], dtype=np.int32)
+        self.T_max, self.n_steps_max = int(self.T.max()), int(self.n_steps.max())
+
+        def stack(name, fill, dtype, rows=self.T_max, lens=self.T):
+            first = np.asarray(getattr(scenes[0], name))
+            out = np.full((S, rows) + first.shape[1:], fill, dtype=dtype)
+            for s, sc in enumerate(scenes):
+                out[s, :lens[s]] = np.asarray(getattr(sc, name))[:lens[s]]
+            return out
+        for name in ('com_tab', 'pose_l', 'pose_r', 'gl_tab', 'gr_tab', 'cur_l', 'cur_r'):
+            setattr(self, name, stack(name, np.nan, np.float64))
+        for name in ('slot_l', 'slot_r', 'step_idx'):
+            setattr(self, name, stack(name, -1, np.int32))
+        for name in ('is_ss', 'support_is_l'):
+            setattr(self, name, stack(name, False, bool))
+        self.plan_pos = stack('plan_pos', np.nan, np.float64, rows=self.n_steps_max, lens=self.n_steps)
+
+    def t_max(self, N, rate=1):
+        """Last valid tick of every scene, (S,)."""
+        return self.T - 1 - (N + 1) * rate
+
+    def build_records(self, spec, t, scene_id, com, dcom, hw, theta_hat, yaw_l, yaw_r, mass, mu, rate=1):
+        """``Scene.build_records`` for a mixed batch: instance b is tick t[b] of scene scene_id[b]."""
+        t, s = np.asarray(t, dtype=np.int64), np.asarray(scene_id, dtype=np.int64)
+        B, N = t.shape[0], spec.N
+        if s.shape != (B,) or (s < 0).any() or (s >= self.S).any():
+            raise ValueError(f"scene_id must hold B indices in [0, {self.S})")
+        if (t < 0).any() or (t + (N + 1) * rate >= self.T[s]).any():
+            raise ValueError("tick outside its scene: need 0 <= t and t + (N+1)*rate < T[scene_id]")
+        rec = np.zeros((B, spec.nrec))
+        rec[:, 0:3], rec[:, 3:6], rec[:, 6:9], rec[:, 9:12] = com, dcom, hw, theta_hat
+        rec[:, 12], rec[:, 13:16] = yaw_l, self.cur_l[s, t]
+        rec[:, 16], rec[:, 17:20] = yaw_r, self.cur_r[s, t]
+        rec[:, 20], rec[:, 21] = mass, mu
+        rec[:, 22], rec[:, 23] = self.gl_tab[s, t + N * rate], self.gr_tab[s, t + N * rate]
+        st = rec[:, 24:].reshape(B, N, 19)
+        tt = t[:, None] + (1 + np.arange(N))[None, :] * rate
+        tn = t[:, None] + np.arange(N)[None, :] * rate
+        ss = s[:, None]
+        st[:, :, 0:9] = self.com_tab[ss, tt]
+        st[:, :, 9:12] = self.pose_l[ss, tt, 3:6]
+        st[:, :, 12:15] = self.pose_r[ss, tt, 3:6]
+        st[:, :, 15] = self.pose_l[ss, tt, 2]
+        st[:, :, 16] = self.pose_r[ss, tt, 2]
+        st[:, :, 17] = self.gl_tab[ss, tn]
+        st[:, :, 18] = self.gr_tab[ss, tn]
+        return rec
+
+    def schedule(self, N, rate=1):
+        """``rollout_schedule`` of every scene, stacked: (cond, is_ds, wb_slot, wb_row), each (S, T_max); padding is
+        False / False / -1 / -1."""
+        S, Tm = self.S, self.T_max
+        cond, is_ds = np.zeros((S, Tm), bool), np.zeros((S, Tm), bool)
+        wb_slot, wb_row = np.full((S, Tm), -1, np.int64), np.full((S, Tm), -1, np.int64)
+        for s, sc in enumerate(self.scenes):
+            c, d, sl, ro = rollout_schedule(sc, N, rate)
+            cond[s, :sc.T], is_ds[s, :sc.T], wb_slot[s, :sc.T], wb_row[s, :sc.T] = c, d, sl, ro
+        return cond, is_ds, wb_slot, wb_row
+
+    def nominal_state(self, t, scene_id):
+        t, s = np.asarray(t, dtype=np.int64), np.asarray(scene_id, dtype=np.int64)
+        com = np.stack([self.com_tab[s, t, 0], self.com_tab[s, t, 1], np.full(t.shape, 0.72)], axis=1)
+        dcom = np.stack([self.com_tab[s, t, 3], self.com_tab[s, t, 4], np.zeros(t.shape)], axis=1)
         return com, dcom
 
 
