@@ -14,6 +14,7 @@
 //     other lanes by v_readlane.  Round 3 kept the matrix in LDS (a read-modify-write per element and update, 48.9 KB per
 //     instance -> three instances per CU); now LDS holds the problem data and the packed factor only (20.7 KB -> seven).
 //     Forward substitution from the registers; the backward one needs the transposed factor and reads it from LDS.
+// The twelve wrench-block pivots of a step are floored at their exact lower bound 1e-6 (rounding loses them otherwise).
 // Failure (status 1 / 2: iteration cap, wrong-inertia pivot, non-finite KKT error) returns zeros in tau, qdd and f_c, as
 // the reference's QPSolver.solve does when OSQP fails (code/utils.py:85-92).
 // The problem data of an instance (Hq, M_b, Jc_b: 8.4 KB) is staged in LDS once; per iteration nothing touches HBM.
@@ -272,7 +273,15 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_kernel(int B, const double *__re
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         const int j = ND + t;
-        const double dj = bcast(w[t], j);
+        double dj = bcast(w[t], j);
+        // The wrench block's pivots are floored at F_REG.  Columns ND .. NX-1 of the matrix are F_REG I + A' diag(z/s) A
+        // next to Hq > 0, so that block of it is >= F_REG I, and so is every Schur complement of it: in exact arithmetic
+        // d_j >= F_REG.  The computed one is a difference of barrier terms of size z/s ~ 1e10 near convergence (a foot's
+        // fz pivot: F_REG + d^2 4 sa sb / (sa + sb) + ...), rounding noise ~ 1e-6 = F_REG, and came out 0 or negative on
+        // one or two feasible instances in a thousand.  fmax also turns a NaN pivot into F_REG: the rest of
+        // that column is NaN then, so is the step, and the next iteration's non-finite test ends in status 2 (the loop's
+        // last turn, it == max_iter, still runs that test; nothing is written out unless a finite KKT error passed it).
+        if (j < NX) dj = fmax(dj, F_REG);
         ok = ok && ((j < NX) ? (dj > 0.0) : (dj < 0.0));
         dl = (ln == j) ? dj : dl;
         const double lij = (ln > j) ? w[t] * pivot_rcp(dj) : 0.0;

@@ -40,9 +40,11 @@ def ineq_matrix(d, mu):
 
 
 def solve(Hq, Fq, M, h, Jc, d, mu_f, tol=TOL, max_iter=MAX_ITER, verbose=False):
-    """One QP.  Hq (30,30) Fq (30,) M (30,30) h (30,) Jc (12,30) -> dict(qdd, f, tau (30,), nu, s, z, status, iters).
-    Primal-dual interior point, monotone barrier schedule, fraction-to-the-boundary steps -- the algorithm of the
-    centroidal MPC solver (oracle/cmpc_oracle.c) on a convex problem (no inertia correction needed)."""
+    """One QP.  Hq (30,30) Fq (30,) M (30,30) h (30,) Jc (12,30) -> dict(qdd, f, tau (30,), nu, s, z, status, iters,
+    kkt, floored).  Primal-dual interior point, monotone barrier schedule, fraction-to-the-boundary steps -- the
+    algorithm of the centroidal MPC solver (oracle/cmpc_oracle.c) on a convex problem (no inertia correction needed).
+    status 0: converged; 1: iteration cap; 2: wrong-inertia pivot or non-finite KKT error -- 1 and 2 with zero outputs,
+    as the kernel.  floored: wrench-block pivots (30 .. 41) raised to F_REG over all Newton steps (`ldl_solve`)."""
     n = ND + NC
     H = np.zeros((n, n)); H[:ND, :ND] = Hq; H[ND:, ND:] = F_REG * np.eye(NC)
     F = np.concatenate([Fq, np.zeros(NC)])
@@ -50,7 +52,7 @@ def solve(Hq, Fq, M, h, Jc, d, mu_f, tol=TOL, max_iter=MAX_ITER, verbose=False):
     Ai = np.hstack([np.zeros((NI, ND)), ineq_matrix(d, mu_f)])
     x = np.zeros(n); nu = np.zeros(NB)
     s = np.maximum(-(Ai @ x), 1.0); mu = MU0; z = mu / s
-    status, it = 1, 0
+    status, it, floored = 1, 0, 0
     for it in range(max_iter + 1):
         rd = H @ x + F + Ae.T @ nu + Ai.T @ z
         rp = Ae @ x - be
@@ -76,7 +78,11 @@ def solve(Hq, Fq, M, h, Jc, d, mu_f, tol=TOL, max_iter=MAX_ITER, verbose=False):
         K[:n, :n] = H + Ai.T @ (sig[:, None] * Ai)
         K[n:, :n] = Ae; K[:n, n:] = Ae.T
         rhs = np.concatenate([-(H @ x + F) - Ai.T @ (mu / s + sig * rg), -rp])
-        sol = ldl_solve(K, rhs, n)
+        sol, nfl = ldl_solve(K, rhs, n, floor_from=ND, floor=F_REG)
+        if sol is None:                         # wrong-inertia pivot (the kernel: status 2, zero outputs)
+            status = 2
+            break
+        floored += nfl
         dx, nu_new = sol[:n], sol[n:]
         ds = -rg - Ai @ dx
         dz = (mu - s * z - z * ds) / s
@@ -90,18 +96,28 @@ def solve(Hq, Fq, M, h, Jc, d, mu_f, tol=TOL, max_iter=MAX_ITER, verbose=False):
     tau = np.zeros(ND)
     if status == 0:
         tau[NB:] = M[NB:, :] @ qdd + h[NB:] - Jc[:, NB:].T @ f
-    return dict(qdd=qdd, f=f, tau=tau, nu=nu, s=s, z=z, status=status, iters=it, kkt=kkt)
+    return dict(qdd=qdd, f=f, tau=tau, nu=nu, s=s, z=z, status=status, iters=it, kkt=kkt, floored=floored)
 
 
-def ldl_solve(K, rhs, n_pos):
+def ldl_solve(K, rhs, n_pos, floor_from=None, floor=0.0):
     """K = L D L' without pivoting (quasi-definite: the first n_pos pivots positive, the rest negative) -- the
-    factorisation the kernel runs, restated densely."""
+    factorisation the kernel runs, restated densely.  Returns (solution, number of floored pivots); the solution is None
+    when a pivot has the wrong sign (or is NaN).
+    Pivots floor_from .. n_pos-1 are floored at `floor` first: there K[:n_pos, :n_pos] = floor * I + (a positive
+    semi-definite matrix) exactly, a Schur complement of a matrix >= floor * I is >= floor * I, so every exact pivot
+    is >= floor and a computed one below it is rounding (the wrench block's fz pivot is a difference of barrier terms of
+    size z / s ~ 1e10 near convergence: noise ~ 1e-6 = F_REG)."""
     m = K.shape[0]
     L = np.tril(K).astype(np.float64).copy()
     dvec = np.zeros(m)
+    floored = 0
     for j in range(m):
         dvec[j] = L[j, j]
-        assert (dvec[j] > 0) == (j < n_pos), "wrong inertia"
+        if floor_from is not None and floor_from <= j < n_pos and not dvec[j] >= floor:
+            dvec[j] = floor                         # (the kernel's fmax: a NaN pivot too -- its column stays NaN, and so
+            floored += 1                            # does the step: the next iteration's non-finite test ends in status 2)
+        if not (dvec[j] > 0 if j < n_pos else dvec[j] < 0):        # (a NaN fails either test, as in the kernel)
+            return None, floored
         col = L[j + 1:, j].copy()
         L[j + 1:, j] = col / dvec[j]
         L[j, j] = 1.0
@@ -113,7 +129,7 @@ def ldl_solve(K, rhs, n_pos):
     y /= dvec
     for j in range(m - 1, -1, -1):
         y[:j] -= L[j, :j] * y[j]
-    return y
+    return y, floored
 
 
 def solve_batch(Hq, Fq, M, h, Jc, d, mu_f, **kw):
@@ -122,9 +138,15 @@ def solve_batch(Hq, Fq, M, h, Jc, d, mu_f, **kw):
     return {k: np.array([o[k] for o in out]) for k in out[0]}
 
 
-def kkt_full(Hq, Fq, M, h, Jc, d, mu_f, qdd, tau, f):
+def kkt_full(Hq, Fq, M, h, Jc, d, mu_f, qdd, tau, f, act_tol=1e-7):
     """KKT residuals of the reference's 72-variable QP (module docstring) at (qdd, tau, f): least-squares multipliers
-    on the active inequality rows.  Returns dict(stationarity, equality, ineq_violation, comp)."""
+    on the active inequality rows.  Returns dict(stationarity, equality, ineq_violation, comp, n_active, z_min).
+    A row counts as active when its slack is below act_tol * max(1, |f|_max).  The interior point stops at
+    s_i z_i <= tol * sd (sd >= 1), so a row with slack s still carries a multiplier up to 1e-9 / s, and a row left out
+    costs that much stationarity: at the default band (slack ~ 1e-5 for forces ~ 100) up to 1e-4 -- a point that is
+    optimal to 1e-9 but has a weakly active row (s ~ z ~ 1e-5) shows 1e-6 .. 1e-5 here.  act_tol = 1e-4 (slack ~ 1e-2,
+    multiplier <= 1e-7) closes that band; what the narrow band stood for -- multipliers on active rows only -- is then
+    `comp` = max_i z_i * slack_i, to be held against the solver's own complementarity bound."""
     n = ND
     nv = 2 * n + NC
     H = np.zeros((nv, nv)); H[:n, :n] = Hq; H[2 * n:, 2 * n:] = F_REG * np.eye(NC)
@@ -135,11 +157,12 @@ def kkt_full(Hq, Fq, M, h, Jc, d, mu_f, qdd, tau, f):
     x = np.concatenate([qdd, tau, f])
     g = H @ x + F
     gi = Ain @ x
-    act = gi > -1e-7 * max(1.0, np.abs(f).max())
+    act = gi > -act_tol * max(1.0, np.abs(f).max())
     # multipliers: g + Aeq' lam + Ain_act' z = 0, z >= 0 (non-negative least squares on z, free lam)
     import scipy.optimize as so
     A = np.hstack([Aeq.T, -Aeq.T, Ain[act].T])
     sol, res = so.nnls(A, -g)
     z = sol[2 * n:]
     return dict(stationarity=res / max(1.0, np.abs(g).max()), equality=np.abs(Aeq @ x - beq).max(),
-                ineq_violation=max(gi.max(), 0.0), n_active=int(act.sum()), z_min=float(z.min()) if z.size else 0.0)
+                ineq_violation=max(gi.max(), 0.0), n_active=int(act.sum()), z_min=float(z.min()) if z.size else 0.0,
+                comp=float((z * np.maximum(-gi[act], 0.0)).max()) if z.size else 0.0)

@@ -1,7 +1,10 @@
 // cmpc_device_unit.hip -- TEST HARNESS ONLY (GPU tier).  The host emulation of the device source (tests/emu) replaces
-// three hand-tuned pieces by plain C++: the Newton pivot square root on v_rsq_f64, the inline-asm LDS batch-read
-// helpers, and the fp64 MFMA tile with its lane layout.  These kernels exercise exactly those pieces on the GPU,
-// in isolation, against values the host computes (tests/test_gpu_device_units.py).
+// seven hand-tuned pieces by plain C++: the Newton pivot square root on v_rsq_f64, the inline-asm LDS batch-read
+// helpers, the fp64 MFMA tile with its lane layout, and the wave primitives -- the butterfly exchange cmpc_pair_of<M>
+// (v_permlane32/16_swap and DPP; the emulation: an exchange through memory), cmpc_bcast (v_readlane), cmpc_uniform_d
+// (v_readfirstlane between hand-counted s_nop) and CMPC_RELANE (the lane id from the execution mask).  These kernels
+// exercise exactly those pieces on the GPU, in isolation, against values the host computes
+// (tests/test_gpu_device_units.py).
 #include <hip/hip_runtime.h>
 #include "../../online-non-linear-centroidal-mpc-with-stability-guarantees-for-robust-locomotion-of-legged-robots-_amd/csrc/cmpc_kernel.hpp"
 
@@ -49,6 +52,60 @@ __global__ void __launch_bounds__(64) k_mfma_tile(const double *A, const double 
   for (int r = 0; r < 4; ++r) Dout[(kq + 4 * r) * 16 + r16] = acc[r];
 }
 
+// cmpc_pair_of<M> for the six distances: a[m][lane], b[m][lane] of one wave, m = 0 .. 5 for M = 32 .. 1.
+__global__ void __launch_bounds__(64) k_pair_of(const double *v, double *a, double *b) {
+  const int lane = threadIdx.x;
+  const double x = v[lane];
+  cmpc_pair_of<32>(x, a[0 * 64 + lane], b[0 * 64 + lane]);
+  cmpc_pair_of<16>(x, a[1 * 64 + lane], b[1 * 64 + lane]);
+  cmpc_pair_of<8>(x, a[2 * 64 + lane], b[2 * 64 + lane]);
+  cmpc_pair_of<4>(x, a[3 * 64 + lane], b[3 * 64 + lane]);
+  cmpc_pair_of<2>(x, a[4 * 64 + lane], b[4 * 64 + lane]);
+  cmpc_pair_of<1>(x, a[5 * 64 + lane], b[5 * 64 + lane]);
+}
+
+// The six-step reductions as the solvers run them (Solver::wave_sum; the bfly_max / bfly_min chains of Solver::red_max /
+// red_min): one wave per vector of 64, every lane's result stored.
+__global__ void __launch_bounds__(64) k_reduce(const double *vs, const double *vm, double *sum, double *mx, double *mn) {
+  typedef cmpc::Solver<4> S;
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  sum[i] = S::wave_sum(vs[i]);
+  double v = vm[i];
+  v = S::bfly_max<32>(v); v = S::bfly_max<16>(v); v = S::bfly_max<8>(v); v = S::bfly_max<4>(v); v = S::bfly_max<2>(v); v = S::bfly_max<1>(v);
+  mx[i] = v;
+  v = vm[i];
+  v = S::bfly_min<32>(v); v = S::bfly_min<16>(v); v = S::bfly_min<8>(v); v = S::bfly_min<4>(v); v = S::bfly_min<2>(v); v = S::bfly_min<1>(v);
+  mn[i] = v;
+}
+
+// src is a kernel argument: a scalar register whose value the compiler does not know
+__global__ void __launch_bounds__(64) k_bcast(const double *v, double *out, int src) {
+  out[src * 64 + threadIdx.x] = cmpc_bcast(v[threadIdx.x], src);
+}
+
+// cmpc_uniform_d between its producer and its consumer: the wave-uniform value comes out of a vector FMA on operands
+// every lane loads for itself (x, y, z hold 64 equal words per value) and goes into a vector multiply by a per-lane
+// factor.  The data dependences leave the compiler nothing to put between the three but what it chooses to.
+__global__ void __launch_bounds__(64) k_uniform_d(const double *x, const double *y, const double *z, const double *fac,
+                                                  double *out, int n) {
+  const int lane = threadIdx.x;
+  const double f = fac[lane];
+#pragma unroll 1
+  for (int i = 0; i < n; ++i) {
+    const double a = x[i * 64 + lane], b = y[i * 64 + lane], c = z[i * 64 + lane];
+    const double u = cmpc_uniform_d(__builtin_fma(a, b, c));
+    out[i * 64 + lane] = u * f;
+  }
+}
+
+// CMPC_RELANE in a two-wave workgroup, as Solver<NV, 2> uses it: lane_base = 64 * wave
+__global__ void __launch_bounds__(128) k_relane(int *out) {
+  const int lane_base = 64 * CMPC_WAVE_ID();
+  int x = -1;
+  CMPC_RELANE(x);
+  out[threadIdx.x] = x;
+}
+
 }  // namespace
 
 extern "C" {
@@ -62,6 +119,26 @@ int unit_lds_helpers(int *bad) {
 }
 int unit_mfma_tile(const double *A, const double *B, double *D) {
   hipLaunchKernelGGL(k_mfma_tile, dim3(1), dim3(64), 0, 0, A, B, D);
+  return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
+}
+int unit_pair_of(const double *v, double *a, double *b) {
+  hipLaunchKernelGGL(k_pair_of, dim3(1), dim3(64), 0, 0, v, a, b);
+  return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
+}
+int unit_reduce(const double *vs, const double *vm, double *sum, double *mx, double *mn, int nvec) {
+  hipLaunchKernelGGL(k_reduce, dim3(nvec), dim3(64), 0, 0, vs, vm, sum, mx, mn);
+  return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
+}
+int unit_bcast(const double *v, double *out) {      // out: 64 x 64, row src
+  for (int src = 0; src < 64; ++src) hipLaunchKernelGGL(k_bcast, dim3(1), dim3(64), 0, 0, v, out, src);
+  return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
+}
+int unit_uniform_d(const double *x, const double *y, const double *z, const double *fac, double *out, int n) {
+  hipLaunchKernelGGL(k_uniform_d, dim3(1), dim3(64), 0, 0, x, y, z, fac, out, n);
+  return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
+}
+int unit_relane(int *out) {
+  hipLaunchKernelGGL(k_relane, dim3(1), dim3(128), 0, 0, out);
   return hipDeviceSynchronize() == hipSuccess ? 0 : 1;
 }
 }

@@ -1,8 +1,11 @@
 """Whole-body inverse-dynamics QP (reference code/inverse_dynamics.py:92-134, code/utils.py:40-92).
 CPU tier: the numpy oracle against the KKT conditions of the reference's own 72-variable statement (the QP is convex:
 a KKT point IS the solution, whatever found it), the host-side cost assembly against a literal loop, the C ABI exports.
-GPU tier: the HIP kernel against the oracle through the C ABI."""
+GPU tier: the HIP kernel against the oracle through the C ABI -- over the parameter matrix (contact phase x foot size x
+friction), past the launch's resident grid, at the iteration cap, on a side stream, and on the instances whose wrench
+pivots are lost to cancellation ("Whole-body QP": the F_REG floor)."""
 import ctypes
+import functools
 import os
 import re
 
@@ -79,6 +82,75 @@ def test_header_symbols_are_exported():
         assert hasattr(raw, n)
 
 
+# ---- the wrench-block pivot floor.  Instance b of wbc_synthetic(32, seed, contact) at half foot size d and
+# friction mu: the fz pivot of a foot's 6 x 6 block (column 35 or 41) comes out <= 0 one or two Newton steps before
+# convergence -- a difference of barrier terms of size z / s ~ 1e10 whose exact value is >= F_REG = 1e-6.
+LOST_PIVOT = [("ds", 3, 0.02, 0.5, 31), ("lfoot", 21, 0.05, 0.3, 3), ("lfoot", 21, 0.05, 0.7, 10), ("rfoot", 21, 0.1, 0.9, 30)]
+CONTACTS = ("ds", "lfoot", "rfoot")
+FOOT_MU = ((0.1, 0.5), (0.1, 0.3), (0.1, 0.7), (0.2, 0.9), (0.04, 0.5))          # (foot_size, mu); d = foot_size / 2
+MATRIX_SEED, MATRIX_B, N_ORACLE = 21, 1024, 16
+
+
+@functools.lru_cache(maxsize=None)
+def _instances(contact, seed, B):
+    """Read-only (instance b does not depend on B: wbc_synthetic draws instance after instance from one stream)."""
+    mats = wl.wbc_synthetic(B, seed=seed, contact=contact)
+    for a in mats:
+        a.setflags(write=False)
+    return mats
+
+
+@functools.lru_cache(maxsize=None)
+def _oracle(contact, seed, B, b, d, mu, tol=wq.TOL, max_iter=wq.MAX_ITER):
+    return wq.solve(*(a[b] for a in _instances(contact, seed, B)), d, mu, tol=tol, max_iter=max_iter)
+
+
+def _kkt_ok(mats, b, d, mu, qdd, tau30, f, eq=1e-8, ineq=1e-9):
+    """The file's thresholds on the reference statement's KKT conditions (CPU tier 1e-6 / 1e-8 / 1e-9, GPU tier 1e-6 /
+    1e-7 / 1e-8), with the active band that does not mistake a weakly active row (s ~ z ~ 1e-5: one double-support
+    instance in six has one) for a stationarity error (kkt_full), and therefore with the complementarity of the
+    multipliers it finds: the solvers stop at s z <= 1e-9 sd, sd = max(1, sum |multipliers| / 2200) -- 1e-8 covers
+    multipliers summing to 22 000, twenty times the robot's weight."""
+    k = wq.kkt_full(*(a[b] for a in mats), d, mu, qdd, tau30, f, act_tol=1e-4)
+    assert k["stationarity"] < 1e-6 and k["equality"] < eq and k["ineq_violation"] < ineq and k["comp"] < 1e-8, (b, k)
+
+
+@pytest.mark.parametrize("contact,seed,d,mu,b", LOST_PIVOT)
+def test_oracle_floors_a_wrench_pivot_lost_to_cancellation(contact, seed, d, mu, b):
+    r = _oracle(contact, seed, 32, b, d, mu)
+    assert r["status"] == 0 and r["floored"] >= 1 and r["iters"] <= 40
+    _kkt_ok(_instances(contact, seed, 32), b, d, mu, r["qdd"], r["tau"], r["f"])
+
+
+def test_oracle_returns_status_2_and_zeros_on_an_indefinite_hessian():
+    Hq, Fq, M, h, Jc = wl.wbc_synthetic(1, seed=5)
+    r = wq.solve(-Hq[0], Fq[0], M[0], h[0], Jc[0], 0.05, 0.5)          # the first pivot is negative: no exception
+    assert r["status"] == 2 and r["iters"] == 0 and r["floored"] == 0
+    assert not r["qdd"].any() and not r["tau"].any() and not r["f"].any()
+
+
+def test_solve_batch_argument_checks_return_before_any_hip_call():
+    """Every rejected call returns 1 with the check's own message (a call that got as far as the HIP runtime would name a
+    HIP error instead, with or without a GPU); B == 0 is a valid empty batch whatever the buffers."""
+    lib = capi.load()
+    bufs = [np.zeros(n) for n in (900, 30, 900, 30, 360, 30, 30, 12)] + [np.zeros(1, dtype=np.int32) for _ in range(2)]
+    ptr = [b.ctypes.data for b in bufs]
+
+    def call(B=1, d=0.05, mu=0.5, tol=1e-9, max_iter=60, null=None):
+        p = [None if i == null else v for i, v in enumerate(ptr)]
+        return lib.cmpc_wbc_qp_solve_batch(0, B, *p[:5], d, mu, tol, max_iter, *p[5:], None)
+
+    assert lib.cmpc_wbc_qp_solve_batch(0, 0, *([None] * 5), 0.05, 0.5, 1e-9, 60, *([None] * 5), None) == 0
+    cases = [(dict(B=-1), b"negative batch")] + [(dict(null=i), b"null buffer") for i in range(10)]
+    cases += [(kw, b"bad argument") for kw in (dict(tol=0.0), dict(tol=-1e-9), dict(tol=float("nan")), dict(max_iter=0),
+                                               dict(max_iter=-3), dict(d=0.0), dict(d=-0.05), dict(d=float("nan")),
+                                               dict(mu=0.0), dict(mu=-0.5), dict(mu=float("nan")))]
+    for kw, msg in cases:
+        assert call(**kw) == 1, kw
+        err = lib.cmpc_wbc_last_error()
+        assert err and msg in err, (kw, err)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("contact,B", [("ds", 300), ("lfoot", 64), ("rfoot", 64)])
 def test_hip_kernel_matches_the_oracle(contact, B):
@@ -126,3 +198,151 @@ def test_hip_kernel_failure_path_returns_zeros_like_the_reference():
     assert bad["status"] == 2 and not bad["qdd"].any() and not bad["tau"].any()
     ref = wq.solve(Hq[3], Fq[3], M[3], h[3], Jc[3], 0.05, 0.5)
     assert np.abs(qdd[3].cpu().numpy() - ref["qdd"]).max() < 1e-6 * max(1.0, np.abs(ref["qdd"]).max())
+
+
+# ---- GPU tier beyond one parameter set
+
+def _dev(a):
+    return torch.from_numpy(np.array(a)).cuda()            # (a writable copy: the cached instances are read-only)
+
+
+def _launch(mats, foot_size, mu, **kw):
+    """One launch on cuda:0; numpy (tau (B,30) with the zero base rows in front, qdd, f, status, iters)."""
+    qp = wbc.BatchedInverseDynamicsQP(foot_size=foot_size, mu=mu, device="cuda:0", **kw)
+    tau, qdd, f, st, it = qp.solve(*(m if torch.is_tensor(m) else _dev(m) for m in mats))
+    torch.cuda.synchronize()
+    tau30 = np.concatenate([np.zeros((tau.shape[0], 6)), tau.cpu().numpy()], axis=1)
+    return tau30, qdd.cpu().numpy(), f.cpu().numpy(), st.cpu().numpy(), it.cpu().numpy()
+
+
+def _assert_parity(out, idx, refs, iters=True):
+    """The parity rule of test_hip_kernel_matches_the_oracle: 1e-6 of the largest entry (at least 1) on tau, qdd and f,
+    iteration counts within 2; rows `idx` of the launch `out` against the oracle's results `refs`."""
+    tau, qdd, f, st, it = out
+    assert all(r["status"] == 0 for r in refs) and (st[idx] == 0).all()
+    for got, key in ((tau, "tau"), (qdd, "qdd"), (f, "f")):
+        ref = np.array([r[key] for r in refs])
+        err = np.abs(got[idx] - ref) / np.maximum(np.abs(ref).max(axis=1, keepdims=True), 1.0)
+        assert err.max() < 1e-6, (key, err.max(axis=1))
+    if iters:
+        assert np.abs(it[idx] - np.array([r["iters"] for r in refs])).max() <= 2
+
+
+def _sample(contact, d, mu, **kw):
+    """The oracle's sample of a class of the parameter matrix: instances 0 .. 15, where the oracle floored no pivot (a
+    floored step is a different step: kernel and oracle need not floor in the same one, and the iteration counts are
+    compared only where neither the rule nor the rounding decides them).  At most one instance gives way to the next
+    one after the sample."""
+    idx = list(range(N_ORACLE))
+    refs = [_oracle(contact, MATRIX_SEED, MATRIX_B, b, d, mu, **kw) for b in idx]
+    swapped = [k for k, r in enumerate(refs) if r["floored"]]
+    assert len(swapped) <= 1
+    for k in swapped:
+        idx[k] = N_ORACLE
+        refs[k] = _oracle(contact, MATRIX_SEED, MATRIX_B, N_ORACLE, d, mu, **kw)
+        assert refs[k]["floored"] == 0
+    return np.array(idx), refs
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("foot_size,mu", FOOT_MU)
+@pytest.mark.parametrize("contact", CONTACTS)
+def test_hip_kernel_over_the_parameter_matrix(contact, foot_size, mu):
+    """1024 instances per class: every one converges to finite outputs (before the pivot floor: profiles/
+    wbc_pivot_floor.json); sixteen against the oracle, four more against the reference statement's KKT conditions."""
+    d = foot_size / 2
+    mats = _instances(contact, MATRIX_SEED, MATRIX_B)
+    out = _launch(mats, foot_size, mu)
+    tau, qdd, f, st, it = out
+    assert (st == 0).all(), np.flatnonzero(st != 0)
+    assert np.isfinite(tau).all() and np.isfinite(qdd).all() and np.isfinite(f).all() and int(it.max()) <= 45
+    idx, refs = _sample(contact, d, mu)
+    _assert_parity(out, idx, refs)
+    for b in (17, 300, 777, MATRIX_B - 1):
+        _kkt_ok(mats, b, d, mu, qdd[b], tau[b], f[b], eq=1e-7, ineq=1e-8)      # (the GPU tier's thresholds, as above)
+    # what the sample covers, from the oracle's multipliers: a row with z > 1e-3 has s < 1e-6 at tol 1e-9 -- active
+    act = np.array([r["z"] for r in refs]) > 1e-3
+    feet = {"ds": (0, 1), "lfoot": (0,), "rfoot": (1,)}[contact]              # (a foot in the air: f ~ 0, every row degenerate)
+    cop = [act[:, 8 * k: 8 * k + 4].any(axis=1) for k in feet]
+    fric = [act[:, 8 * k + 4: 8 * k + 8].any(axis=1) for k in feet]
+    assert np.any(cop) and np.any(fric)
+    if contact == "ds":
+        assert (act[:, :8].any(axis=1) & act[:, 8:].any(axis=1)).any()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("contact,seed,d,mu,b", LOST_PIVOT)
+def test_hip_kernel_solves_the_lost_pivot_instances(contact, seed, d, mu, b):
+    """The QP is strictly convex: one solution, whichever steps kernel and oracle floor in (no iteration parity)."""
+    mats = _instances(contact, seed, 32)
+    out = _launch(mats, 2 * d, mu)
+    tau, qdd, f, st, it = out
+    assert st[b] == 0 and (st == 0).all()
+    _assert_parity(out, np.array([b]), [_oracle(contact, seed, 32, b, d, mu)], iters=False)
+    _kkt_ok(mats, b, d, mu, qdd[b], tau[b], f[b], eq=1e-7, ineq=1e-8)
+
+
+@pytest.mark.gpu
+def test_hip_kernel_past_the_resident_grid():
+    """The launch's grid is 7 workgroups per CU; a longer batch goes round the instance loop.  B > 2 grids, tiled from 257
+    distinct instances (257 is prime to the grid: the copies of an instance land in different workgroups, at different
+    turns of the loop, behind different predecessors), the three contact phases interleaved, an indefinite Hessian and
+    a NaN planted among them -- below the grid and above it, each followed by good instances in its workgroup.  Nothing
+    an instance leaves in LDS (x, the packed factor, the constant Schur complement) or in registers may reach the
+    next: every row is bit for bit the row of a launch of the 257 alone, one instance per workgroup."""
+    grid = torch.cuda.get_device_properties(0).multi_processor_count * 7
+    B, U = 2 * grid + 515, 257
+    assert B > 2 * grid and grid % U != 0 and U < grid
+    per = [_instances(c, MATRIX_SEED, MATRIX_B) for c in CONTACTS]
+    base = [np.stack([per[i % 3][k][i // 3] for i in range(U)]) for k in range(5)]
+    bad_h, bad_f = (5, 100, 256), (50, 200)
+    for i in bad_h:
+        base[0][i] = -base[0][i]
+    for i in bad_f:
+        base[1][i, 3] = np.nan
+    ref = _launch(base, 0.1, 0.5)
+    rows = np.arange(B) % U
+    got = _launch([_dev(a)[torch.from_numpy(rows).cuda()].contiguous() for a in base], 0.1, 0.5)
+    planted = np.isin(rows, bad_h + bad_f)
+    assert planted[:grid].sum() >= 5 and planted[grid:].sum() >= 5
+    assert (ref[3][list(bad_h + bad_f)] == 2).all() and (np.delete(ref[3], bad_h + bad_f) == 0).all()
+    for i in bad_h + bad_f:
+        assert not ref[0][i].any() and not ref[1][i].any() and not ref[2][i].any()
+    for g, r, name in zip(got, ref, ("tau", "qdd", "f", "status", "iters")):
+        assert g.dtype == r.dtype and np.array_equal(g.view(np.uint8), r[rows].view(np.uint8)), name
+
+
+@pytest.mark.gpu
+def test_hip_kernel_iteration_cap_and_looser_tolerance():
+    """status 1 = out of iterations, zeros out (the reference's QPSolver returns zeros when OSQP fails): an instance the
+    oracle solves in k iterations converges under max_iter = k and does not under k - 1, in kernel and oracle alike."""
+    mats = _instances("ds", MATRIX_SEED, MATRIX_B)
+    for b in range(4):
+        one = [a[b:b + 1] for a in mats]
+        k = _oracle("ds", MATRIX_SEED, MATRIX_B, b, 0.05, 0.5)["iters"]
+        tau, qdd, f, st, it = _launch(one, 0.1, 0.5, max_iter=k)
+        assert st[0] == 0 and it[0] == k and qdd.any()
+        tau, qdd, f, st, it = _launch(one, 0.1, 0.5, max_iter=k - 1)
+        assert st[0] == 1 and it[0] == k - 1
+        assert not tau.any() and not qdd.any() and not f.any()
+        capped = wq.solve(*(a[0] for a in one), 0.05, 0.5, max_iter=k - 1)
+        assert capped["status"] == 1 and capped["iters"] == k - 1 and not capped["qdd"].any() and not capped["tau"].any()
+    idx, refs = _sample("ds", 0.05, 0.5, tol=1e-6)
+    tight = [_oracle("ds", MATRIX_SEED, MATRIX_B, b, 0.05, 0.5)["iters"] for b in idx]
+    assert sum(r["iters"] for r in refs) <= sum(tight) - N_ORACLE // 2          # (the tolerance did reach the solver)
+    _assert_parity(_launch([a[:N_ORACLE + 1] for a in mats], 0.1, 0.5, tol=1e-6), idx, refs)
+
+
+@pytest.mark.gpu
+def test_hip_kernel_on_a_side_stream():
+    mats = [_dev(a[:64]) for a in _instances("ds", MATRIX_SEED, MATRIX_B)]
+    qp = wbc.BatchedInverseDynamicsQP(foot_size=0.1, mu=0.5, device="cuda:0")
+    want = [t.cpu().numpy() for t in qp.solve(*mats)]
+    side = torch.cuda.Stream(device="cuda:0")
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        got = qp.solve(*mats)
+    side.synchronize()
+    assert int(want[3].max()) == 0
+    for g, w in zip(got, want):
+        assert np.array_equal(g.cpu().numpy().view(np.uint8), w.view(np.uint8))
