@@ -32,10 +32,46 @@ extern "C" {
 #define CMPC_WBC_BASE 6
 #define CMPC_WBC_CONTACT 12
 #define CMPC_WBC_INEQ 16
+#define CMPC_WBC_TASK_ROWS 21 /* lfoot 6, rfoot 6, com 3, torso 3, base 3: the Jacobians of :46-51, stacked in that order */
+#define CMPC_WBC_NACC (CMPC_WBC_TASK_ROWS + CMPC_WBC_DOFS) /* 51: the 21 task rows, then the 30 rows of the joint task */
+
+/* weights and gains of the six tasks, in the order lfoot, rfoot, com, torso, base, joints (:41-44) */
+typedef struct cmpc_wbc_gains {
+  int32_t struct_size, reserved; /* struct_size = sizeof(cmpc_wbc_gains), checked by the entry point */
+  double weight[6], pos_gain[6], vel_gain[6];
+} cmpc_wbc_gains;
 
 int cmpc_wbc_qp_solve_batch(int device, int32_t B, const double *Hq, const double *Fq, const double *M, const double *h,
                             const double *Jc, double half_foot_size, double mu, double tol, int32_t max_iter,
                             double *tau, double *qdd, double *f_c, int32_t *status, int32_t *iters, void *stream);
+
+/* The literals of code/inverse_dynamics.py:42-44 (and struct_size). */
+void cmpc_wbc_default_gains(cmpc_wbc_gains *g);
+
+/*
+ * The same QP from the task form of code/inverse_dynamics.py:46-103, with the parameters of instance b in row b:
+ *   J        [B][21][30]  task Jacobians (:46-51), rows lfoot 6, rfoot 6, com 3, torso 3, base 3
+ *   Jdot     [B][21][30]  their derivatives (:60-64); NULL = the caller folded -Jdot qd into acc_ff (qd is not read then)
+ *   acc_ff   [B][51]      feed-forward accelerations (:68-73): the 21 task rows, then the 30 joints
+ *   pos_err  [B][51]      (:76-81)        vel_err [B][51]  (:84-89)
+ *   qd       [B][30]      current['joint']['vel']
+ *   joint_sel[30]         diagonal of joint_selection (:24-28), shared by the batch
+ *   M, h                  as above
+ *   contact  [B][2]       left, right contact flag: multiplies that foot's Jacobian rows in Jc (:114)
+ *   foot_mu  [B][2]       half foot size d, friction coefficient mu of instance b
+ *   gains                 HOST pointer, read before the call returns
+ * Hq = sum_t w_t J_t' J_t and Fq = -sum_t w_t J_t' (ff + k_v e_v + k_p e_p - Jdot_t qd) (:98-106; the joint task adds
+ * w diag(sel^2) and -w sel (ff + k_v e_v + k_p e_p)) are formed on the device, Jc = [contact_l J[0:6]; contact_r J[6:12]];
+ * instance b then solves exactly the QP of cmpc_wbc_qp_solve_batch with d, mu of its row of foot_mu.  Outputs and status
+ * as above.  Rows are checked on the device: a row of foot_mu that is not finite and > 0 gives status 2, iters 0 and
+ * zero outputs for that instance alone; any other non-finite input ends in status 2 with zeros as well.
+ * Asynchronous on `stream`; allocates nothing (capturable in a HIP graph).
+ */
+int cmpc_wbc_qp_solve_tasks(int device, int32_t B, const double *J, const double *Jdot, const double *acc_ff,
+                            const double *pos_err, const double *vel_err, const double *qd, const double *joint_sel,
+                            const double *M, const double *h, const double *contact, const double *foot_mu,
+                            const cmpc_wbc_gains *gains, double tol, int32_t max_iter, double *tau, double *qdd,
+                            double *f_c, int32_t *status, int32_t *iters, void *stream);
 const char *cmpc_wbc_last_error(void);
 
 #ifdef __cplusplus

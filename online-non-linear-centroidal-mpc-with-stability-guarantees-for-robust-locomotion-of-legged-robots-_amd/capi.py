@@ -22,7 +22,14 @@ SYMBOLS = ("cmpc_default_spec", "cmpc_create", "cmpc_destroy", "cmpc_workspace_b
            "cmpc_tables_set_plan_slots", "cmpc_build_records_planned",
            "cmpc_scenes_create", "cmpc_build_records_scenes", "cmpc_scenes_set_schedule", "cmpc_rollout_advance")
 #: every symbol include/cmpc_wbc.h declares (batched whole-body QP, same library)
-WBC_SYMBOLS = ("cmpc_wbc_qp_solve_batch", "cmpc_wbc_last_error")
+WBC_SYMBOLS = ("cmpc_wbc_qp_solve_batch", "cmpc_wbc_qp_solve_tasks", "cmpc_wbc_default_gains", "cmpc_wbc_last_error")
+
+
+class WbcGains(ctypes.Structure):
+    """``cmpc_wbc_gains`` of include/cmpc_wbc.h; task order lfoot, rfoot, com, torso, base, joints."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("weight", ctypes.c_double * 6),
+                ("pos_gain", ctypes.c_double * 6), ("vel_gain", ctypes.c_double * 6)]
+
 
 _lib = None
 
@@ -83,6 +90,10 @@ def load():
     f64 = ctypes.c_double
     lib.cmpc_wbc_qp_solve_batch.argtypes = [ctypes.c_int, i32, vp, vp, vp, vp, vp, f64, f64, f64, i32, vp, vp, vp, vp, vp, vp]
     lib.cmpc_wbc_qp_solve_batch.restype = ctypes.c_int
+    lib.cmpc_wbc_qp_solve_tasks.argtypes = [ctypes.c_int, i32] + [vp] * 11 + [ctypes.POINTER(WbcGains), f64, i32] + [vp] * 6
+    lib.cmpc_wbc_qp_solve_tasks.restype = ctypes.c_int
+    lib.cmpc_wbc_default_gains.argtypes = [ctypes.POINTER(WbcGains)]
+    lib.cmpc_wbc_default_gains.restype = None
     lib.cmpc_wbc_last_error.argtypes = []
     lib.cmpc_wbc_last_error.restype = ctypes.c_char_p
     lib.cmpc_version.argtypes = []

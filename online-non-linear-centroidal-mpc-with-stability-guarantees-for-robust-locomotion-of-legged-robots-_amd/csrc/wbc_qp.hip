@@ -19,9 +19,13 @@
 // the reference's QPSolver.solve does when OSQP fails (code/utils.py:85-92).
 // The problem data of an instance (Hq, M_b, Jc_b: 8.4 KB) is staged in LDS once; per iteration nothing touches HBM.
 // Instances are independent: workgroups stride over the batch, no inter-workgroup communication.
+// Two entry points, one Newton loop: cmpc_wbc_qp_solve_batch takes Hq, Fq, Jc and one (d, mu) per launch (wbc_qp_kernel);
+// cmpc_wbc_qp_solve_tasks takes the task Jacobians, forms Hq, Fq and Jc in LDS and reads d, mu and the contact flags per
+// instance (wbc_tasks_qp_kernel).  Same LDS image, same residency.
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/cmpc_wbc.h"
 #include "cmpc_wave.hpp"
@@ -78,6 +82,15 @@ __device__ __forceinline__ double bcast(double v, int src) {
   return u.d;
 }
 
+// a value every lane holds alike, moved to scalar registers (the instance's own d, mu, flags: loaded after other
+// instances' stores, they would arrive by vector loads and stay in vector registers across the Newton loop)
+__device__ __forceinline__ double uniform(double v) {
+  union { double d; int i[2]; } u; u.d = v;
+  u.i[0] = __builtin_amdgcn_readfirstlane(u.i[0]);
+  u.i[1] = __builtin_amdgcn_readfirstlane(u.i[1]);
+  return u.d;
+}
+
 // entry (r, c) of the 8 x 6 wrench rows of code/inverse_dynamics.py:116-123; a wrench is [moment(3), force(3)]
 __device__ __forceinline__ double wrench_entry(int r, int c, double d, double mu) {
   const int pair = r >> 1;                         // 0: mx, 1: my, 2: fx, 3: fy
@@ -88,22 +101,115 @@ __device__ __forceinline__ double wrench_entry(int r, int c, double d, double mu
   return 0.0;
 }
 
-__global__ void __launch_bounds__(64, 2) wbc_qp_kernel(int B, const double *__restrict__ Hq, const double *__restrict__ Fq,
-                                                    const double *__restrict__ M, const double *__restrict__ hvec,
-                                                    const double *__restrict__ Jc, double dfoot, double muf, double tol,
-                                                    int max_iter, double *__restrict__ tau, double *__restrict__ qdd,
-                                                    double *__restrict__ fc, int32_t *__restrict__ status,
-                                                    int32_t *__restrict__ iters) {
+// The two forms the problem arrives in (include/cmpc_wbc.h).
+// THE NAMES OF THESE TWO STRUCTS ARE LOAD-BEARING: the kernels are instances of one template and differ, in their symbols,
+// only by the name of their argument struct.  tests/test_capi.py finds the matrix kernel as the first symbol that contains
+// "wbc_qp_kernel", tests/test_wbc_tasks_resources.py finds the other by "wbc_tasks_qp_kernel" -- which must not contain the
+// first string.  Rename one and those lookups fail (or, worse, pick the wrong kernel).
+// Matrices: Hq, Fq, Jc; one d, mu for the launch.
+struct wbc_qp_kernel_args {
+  const double *Hq, *Fq, *Jc;
+  double dfoot, muf;
+};
+// Tasks: the Jacobians, accelerations and errors Hq and Fq are made of, d, mu and the contact flags of every instance;
+// the gains by value.
+constexpr int NT_ROWS = CMPC_WBC_TASK_ROWS, NA = CMPC_WBC_NACC;
+struct wbc_tasks_qp_kernel_args {
+  const double *J, *Jdot, *ff, *pe, *ve, *qd, *sel, *contact, *foot_mu;
+  cmpc_wbc_gains g;
+};
+// J (21 x 31) and the commanded accelerations (51) of the instance being staged live where the packed factor will: that
+// region is not written before the constant part of the factorisation is over, and Hq, Fq and Jc_b are formed by then.
+constexpr int oJ = oL, oA = oJ + NT_ROWS * HS;
+static_assert(oA + NA <= oC, "task staging must fit in the packed-factor region");
+__device__ __forceinline__ constexpr int task_of(int r) { return r < 6 ? 0 : r < 12 ? 1 : r < 15 ? 2 : r < 18 ? 3 : r < NT_ROWS ? 4 : 5; }
+
+// Both kernels are this template: everything from the initial point to the status write is one body, the staging
+// prologue and the Jc of the tau epilogue depend on the form.  (A kernel template, not a device function called from two
+// kernels: hipcc optimises an inlined callee twice, and wbc_qp_kernel came out with other registers.  Each instance
+// carries the name of its argument form in its symbol: wbc_qp_kernel, wbc_tasks_qp_kernel below.)
+template <class Args>
+__global__ void __launch_bounds__(64, 2) wbc_ipm_kernel(int B, Args in, const double *__restrict__ M,
+                                                     const double *__restrict__ hvec, double tol, int max_iter,
+                                                     double *__restrict__ tau, double *__restrict__ qdd,
+                                                     double *__restrict__ fc, int32_t *__restrict__ status,
+                                                     int32_t *__restrict__ iters) {
+  constexpr bool TASKS = std::is_same<Args, wbc_tasks_qp_kernel_args>::value;
   __shared__ double L[LDS_DOUBLES];
   const int lane = threadIdx.x;
+  double dfoot = 0.0, muf = 0.0;
+  if constexpr (!TASKS) { dfoot = in.dfoot; muf = in.muf; }
   for (int b = blockIdx.x; b < B; b += gridDim.x) {
-    const double *Hb = Hq + (size_t)b * ND * ND, *Mb = M + (size_t)b * ND * ND, *Jb = Jc + (size_t)b * NC * ND;
-    // ---- stage the instance: Hq, the base rows of M, the base columns of Jc, Fq, h_b
-    for (int e = lane; e < ND * ND; e += 64) L[oH + (e / ND) * HS + e % ND] = Hb[e];
-    for (int e = lane; e < NB * ND; e += 64) L[oMB + (e / ND) * HS + e % ND] = Mb[e];
-    for (int e = lane; e < NC * NB; e += 64) L[oJB + (e / NB) * 7 + e % NB] = Jb[(e / NB) * ND + e % NB];
-    if (lane < NX) L[oF + lane] = (lane < ND) ? Fq[(size_t)b * ND + lane] : 0.0;
-    if (lane < NB) L[oHB + lane] = hvec[(size_t)b * ND + lane];
+    const double *Mb = M + (size_t)b * ND * ND, *Jb;
+    if constexpr (!TASKS) {
+      const double *Hb = in.Hq + (size_t)b * ND * ND, *Fq = in.Fq;
+      Jb = in.Jc + (size_t)b * NC * ND;
+      // ---- stage the instance: Hq, the base rows of M, the base columns of Jc, Fq, h_b
+      for (int e = lane; e < ND * ND; e += 64) L[oH + (e / ND) * HS + e % ND] = Hb[e];
+      for (int e = lane; e < NB * ND; e += 64) L[oMB + (e / ND) * HS + e % ND] = Mb[e];
+      for (int e = lane; e < NC * NB; e += 64) L[oJB + (e / NB) * 7 + e % NB] = Jb[(e / NB) * ND + e % NB];
+      if (lane < NX) L[oF + lane] = (lane < ND) ? Fq[(size_t)b * ND + lane] : 0.0;
+      if (lane < NB) L[oHB + lane] = hvec[(size_t)b * ND + lane];
+    } else {
+      const wbc_tasks_qp_kernel_args &ta = in;
+      Jb = in.J + (size_t)b * NT_ROWS * ND;
+      // ---- the instance's own d, mu (wave-uniform), checked here: a bad row fails alone, before anything is staged
+      dfoot = uniform(ta.foot_mu[2 * (size_t)b]);
+      muf = uniform(ta.foot_mu[2 * (size_t)b + 1]);
+      if (!(dfoot > 0.0 && dfoot < INFINITY && muf > 0.0 && muf < INFINITY)) {
+        if (lane < ND) { qdd[(size_t)b * ND + lane] = 0.0; tau[(size_t)b * ND + lane] = 0.0; }
+        if (lane < NC) fc[(size_t)b * NC + lane] = 0.0;
+        if (lane == 0) { status[b] = 2; iters[b] = 0; }
+        continue;
+      }
+      const double cl = uniform(ta.contact[2 * (size_t)b]), cr = uniform(ta.contact[2 * (size_t)b + 1]);
+      // ---- stage J, the base rows of M, h_b; commanded accelerations a = ff + k_v e_v + k_p e_p - Jdot qd (task row
+      // `lane`) and the joint task's (joint `lane`, no Jdot term)
+      for (int e = lane; e < NT_ROWS * ND; e += 64) L[oJ + (e / ND) * HS + e % ND] = Jb[e];
+      for (int e = lane; e < NB * ND; e += 64) L[oMB + (e / ND) * HS + e % ND] = Mb[e];
+      if (lane < NB) L[oHB + lane] = hvec[(size_t)b * ND + lane];
+      const double *ffb = ta.ff + (size_t)b * NA, *peb = ta.pe + (size_t)b * NA, *veb = ta.ve + (size_t)b * NA;
+      if (lane < NT_ROWS) {
+        const int t = task_of(lane);
+        double a = __builtin_fma(ta.g.pos_gain[t], peb[lane], __builtin_fma(ta.g.vel_gain[t], veb[lane], ffb[lane]));
+        if (ta.Jdot) {                                       // (uniform)
+          const double *jd = ta.Jdot + ((size_t)b * NT_ROWS + lane) * ND, *qdb = ta.qd + (size_t)b * ND;
+          double jq = 0.0;
+          for (int j = 0; j < ND; ++j) jq = __builtin_fma(jd[j], qdb[j], jq);
+          a -= jq;
+        }
+        L[oA + lane] = a;
+      }
+      if (lane < ND)
+        L[oA + NT_ROWS + lane] = __builtin_fma(ta.g.pos_gain[5], peb[NT_ROWS + lane],
+                                               __builtin_fma(ta.g.vel_gain[5], veb[NT_ROWS + lane], ffb[NT_ROWS + lane]));
+      lds_fence();
+      // ---- Hq, Fq (code/inverse_dynamics.py:98-106): lane i forms row i.  The product J[r][i] J[r][j] is rounded before
+      // the weight is applied and the sum runs over r in one order, so the row-i word j and the row-j word i are the same
+      // double: the residuals read full rows of Hq, the factorisation its lower triangle.
+      if (lane < ND) {
+        double jc[NT_ROWS];
+#pragma unroll
+        for (int r = 0; r < NT_ROWS; ++r) jc[r] = L[oJ + r * HS + lane];
+        const double sl = ta.sel[lane], wj = ta.g.weight[5];
+        for (int j = 0; j < ND; ++j) {
+          double acc = 0.0;
+#pragma unroll
+          for (int r = 0; r < NT_ROWS; ++r) {
+            const double p = jc[r] * L[oJ + r * HS + j];
+            acc = __builtin_fma(ta.g.weight[task_of(r)], p, acc);
+          }
+          if (j == lane) acc = __builtin_fma(wj, sl * sl, acc);
+          L[oH + lane * HS + j] = acc;
+        }
+        double f = 0.0;
+#pragma unroll
+        for (int r = 0; r < NT_ROWS; ++r) f = __builtin_fma(ta.g.weight[task_of(r)] * jc[r], L[oA + r], f);
+        f = __builtin_fma(wj * sl, L[oA + NT_ROWS + lane], f);
+        L[oF + lane] = -f;
+      } else if (lane < NX) L[oF + lane] = 0.0;
+      for (int e = lane; e < NC * NB; e += 64) L[oJB + (e / NB) * 7 + e % NB] = ((e / NB < 6) ? cl : cr) * L[oJ + (e / NB) * HS + e % NB];
+    }
     // ---- initial point: x = 0, nu = 0, s = 1, z = mu / s
     double mu = MU0;
     if (lane < NX) L[oX + lane] = 0.0;
@@ -375,7 +481,12 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_kernel(int B, const double *__re
       if (lane >= NB && good) {
         t = hvec[(size_t)b * ND + lane];
         for (int j = 0; j < ND; ++j) t += Mb[lane * ND + j] * L[oX + j];
-        for (int c = 0; c < NC; ++c) t -= Jb[c * ND + lane] * L[oX + ND + c];
+        if constexpr (!TASKS) {
+          for (int c = 0; c < NC; ++c) t -= Jb[c * ND + lane] * L[oX + ND + c];
+        } else {                                             // Jc = the feet's rows of J, scaled by the instance's flags
+          const double cl = in.contact[2 * (size_t)b], cr = in.contact[2 * (size_t)b + 1];
+          for (int c = 0; c < NC; ++c) t -= ((c < 6) ? cl : cr) * Jb[c * ND + lane] * L[oX + ND + c];
+        }
       }
       tau[(size_t)b * ND + lane] = t;
     }
@@ -384,7 +495,35 @@ __global__ void __launch_bounds__(64, 2) wbc_qp_kernel(int B, const double *__re
   }
 }
 
+constexpr auto wbc_qp_kernel = wbc_ipm_kernel<wbc_qp_kernel_args>;
+constexpr auto wbc_tasks_qp_kernel = wbc_ipm_kernel<wbc_tasks_qp_kernel_args>;
+
 thread_local std::string g_wbc_err;
+
+// Device, CU count and grid of a launch over B instances (shared by the entry points); *prev = the caller's device.
+int wbc_launch_grid(int device, int B, int *prev, const char *who) {
+  *prev = -1;
+  if (hipGetDevice(prev) != hipSuccess) *prev = -1;
+  if (*prev != device && hipSetDevice(device) != hipSuccess) { g_wbc_err = std::string(who) + ": bad device"; return -1; }
+  // CU count per device, queried once (hipGetDeviceProperties is a slow host call; this entry point runs every tick)
+  static int cu_cache[64] = {0};
+  int cus = (device >= 0 && device < 64) ? cu_cache[device] : 0;
+  if (cus <= 0) {
+    hipDeviceProp_t prop;
+    cus = (hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 256;
+    if (device >= 0 && device < 64) cu_cache[device] = cus;
+  }
+  const int per_cu = (int)((160 * 1024) / (sizeof(double) * LDS_DOUBLES + 64));       // LDS-limited residency
+  const int grid = cus * (per_cu < 1 ? 1 : per_cu);
+  return B < grid ? B : grid;
+}
+
+int wbc_launch_done(int device, int prev, const char *who) {
+  const hipError_t e = hipGetLastError();
+  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
+  if (e != hipSuccess) { g_wbc_err = std::string(who) + ": " + hipGetErrorString(e); return 1; }
+  return 0;
+}
 
 }  // namespace
 
@@ -397,26 +536,38 @@ int cmpc_wbc_qp_solve_batch(int device, int32_t B, const double *Hq, const doubl
   if (B == 0) return 0;
   if (!Hq || !Fq || !M || !h || !Jc || !tau || !qdd || !f_c || !status || !iters) { g_wbc_err = "cmpc_wbc_qp_solve_batch: null buffer"; return 1; }
   if (!(tol > 0) || max_iter < 1 || !(half_foot_size > 0) || !(mu > 0)) { g_wbc_err = "cmpc_wbc_qp_solve_batch: bad argument"; return 1; }
-  int prev = -1;
-  if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-  if (prev != device && hipSetDevice(device) != hipSuccess) { g_wbc_err = "cmpc_wbc_qp_solve_batch: bad device"; return 1; }
-  // CU count per device, queried once (hipGetDeviceProperties is a slow host call; this entry point runs every tick)
-  static int cu_cache[64] = {0};
-  int cus = (device >= 0 && device < 64) ? cu_cache[device] : 0;
-  if (cus <= 0) {
-    hipDeviceProp_t prop;
-    cus = (hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 256;
-    if (device >= 0 && device < 64) cu_cache[device] = cus;
-  }
-  const int per_cu = (int)((160 * 1024) / (sizeof(double) * LDS_DOUBLES + 64));       // LDS-limited residency
-  int grid = cus * (per_cu < 1 ? 1 : per_cu);
-  if (B < grid) grid = B;
-  hipLaunchKernelGGL(wbc_qp_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, B, Hq, Fq, M, h, Jc, half_foot_size, mu,
-                     tol, max_iter, tau, qdd, f_c, status, iters);
-  const hipError_t e = hipGetLastError();
-  if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
-  if (e != hipSuccess) { g_wbc_err = std::string("cmpc_wbc_qp_solve_batch: ") + hipGetErrorString(e); return 1; }
-  return 0;
+  int prev;
+  const int grid = wbc_launch_grid(device, B, &prev, "cmpc_wbc_qp_solve_batch");
+  if (grid < 0) return 1;
+  hipLaunchKernelGGL(wbc_qp_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, B,
+                     wbc_qp_kernel_args{Hq, Fq, Jc, half_foot_size, mu}, M, h, tol, max_iter, tau, qdd, f_c, status, iters);
+  return wbc_launch_done(device, prev, "cmpc_wbc_qp_solve_batch");
+}
+
+void cmpc_wbc_default_gains(cmpc_wbc_gains *g) {             // code/inverse_dynamics.py:42-44
+  const cmpc_wbc_gains d = {(int32_t)sizeof(cmpc_wbc_gains), 0, {1.0, 1.0, 1.0, 1.0, 1.0, 1.0e-1},
+                            {10.0, 10.0, 5.0, 10.0, 10.0, 10.0}, {5.0, 5.0, 10.0, 5.0, 3.0, 5.0}};
+  if (g) *g = d;
+}
+
+int cmpc_wbc_qp_solve_tasks(int device, int32_t B, const double *J, const double *Jdot, const double *acc_ff,
+                            const double *pos_err, const double *vel_err, const double *qd, const double *joint_sel,
+                            const double *M, const double *h, const double *contact, const double *foot_mu,
+                            const cmpc_wbc_gains *gains, double tol, int32_t max_iter, double *tau, double *qdd,
+                            double *f_c, int32_t *status, int32_t *iters, void *stream) {
+  if (B < 0) { g_wbc_err = "cmpc_wbc_qp_solve_tasks: negative batch"; return 1; }
+  if (B == 0) return 0;
+  if (!J || !acc_ff || !pos_err || !vel_err || (Jdot && !qd) || !joint_sel || !M || !h || !contact || !foot_mu || !gains ||
+      !tau || !qdd || !f_c || !status || !iters) { g_wbc_err = "cmpc_wbc_qp_solve_tasks: null buffer"; return 1; }
+  if (!(tol > 0) || max_iter < 1) { g_wbc_err = "cmpc_wbc_qp_solve_tasks: bad argument"; return 1; }
+  if (gains->struct_size != (int32_t)sizeof(cmpc_wbc_gains)) { g_wbc_err = "cmpc_wbc_qp_solve_tasks: bad gains struct_size"; return 1; }
+  int prev;
+  const int grid = wbc_launch_grid(device, B, &prev, "cmpc_wbc_qp_solve_tasks");
+  if (grid < 0) return 1;
+  const wbc_tasks_qp_kernel_args ta = {J, Jdot, acc_ff, pos_err, vel_err, qd, joint_sel, contact, foot_mu, *gains};
+  hipLaunchKernelGGL(wbc_tasks_qp_kernel, dim3(grid), dim3(64), 0, (hipStream_t)stream, B, ta, M, h, tol, max_iter, tau, qdd,
+                     f_c, status, iters);
+  return wbc_launch_done(device, prev, "cmpc_wbc_qp_solve_tasks");
 }
 
 const char *cmpc_wbc_last_error(void) { return g_wbc_err.c_str(); }

@@ -13,7 +13,8 @@ twin of this loop is ``walk.WalkHarness`` around the drop-in class):
      prediction or an exogenous measured signal ``hw_measured[t] (+ per-instance offset)`` (see walk.py).
   4. optionally the consumer of the tick, the whole-body inverse-dynamics QP (code/inverse_dynamics.py:30-134, called
      from code/simulation.py:214-232 with ``desired['com']`` = the MPC's CoM position / velocity / acceleration): a
-     batched ``wbc.BatchedInverseDynamicsQP`` fed by the caller's rigid-body model (``attach_whole_body``), so that the
+     batched ``wbc.BatchedInverseDynamicsQP`` fed by the caller's rigid-body model (``attach_whole_body``, or from the task
+     Jacobians with every instance's own contact flags and friction: ``attach_whole_body_tasks``), so that the
      whole tick -- records, MPC solve, write-back, QP -- stays on the device.
 Everything after the solve is index arithmetic and copies in torch (device memory plumbing); the schedule
 (phases, step indices) is shared by the batch, the plan positions are per instance.
@@ -126,8 +127,30 @@ class BatchedRollout:
         reference, code/inverse_dynamics.py:46-66, :107-111) and ``desired`` = dict(com_pos, com_vel, com_acc (B,3),
         gamma_l, gamma_r (B,)) -- what code/simulation.py:214-232 hands over from the MPC's ``model_state``.  The
         result of the last tick is kept in ``last_wbc`` = (tau (B,24), qdd, f_c, status, iters)."""
-        self._wbc = (qp, model)
+        self._wbc = (qp, model, None)
         self.last_wbc = None
+
+    def attach_whole_body_tasks(self, qp, model, mu=None, foot_size=None):
+        """``attach_whole_body`` from the task form: ``model(rollout, desired)`` returns the task inputs of
+        ``qp.solve_tasks`` -- (J, Jdot, ff, pos_error, vel_error, qd, M, h[, joint_selection[, gains]]) -- and the rollout
+        supplies the rest per instance: contact = (gamma_l, gamma_r) of the instance's own scene and tick, mu = the
+        friction the MPC runs with (``state[:, 15]``) unless given here, foot_size (default: the qp's)."""
+        self._wbc = (qp, model, dict(mu=mu, foot_size=foot_size))
+        self.last_wbc = None
+
+    def _whole_body(self, x1, u0):
+        """The consumer of the tick: whole-body QP on the same stream, no host hop."""
+        if self._wbc is None:
+            return
+        qp, model, tasks = self._wbc
+        desired = self.desired_com(x1, u0, self.t)
+        if tasks is None:
+            self.last_wbc = qp.solve(*model(self, desired))
+            return
+        args = tuple(model(self, desired))
+        contact = torch.stack([desired["gamma_l"], desired["gamma_r"]], dim=1).to(torch.float64).contiguous()
+        mu = self.state[:, 15].contiguous() if tasks["mu"] is None else tasks["mu"]
+        self.last_wbc = qp.solve_tasks(*args[:8], contact, mu, tasks["foot_size"], *args[8:])
 
     def desired_com(self, x1, u0, t):
         """``model_state['com']`` of the reference's back half (:633-649) for the batch: position and velocity of x_1 and
@@ -189,9 +212,7 @@ class BatchedRollout:
         x1 = XU[:, 20:40]
         u0 = XU[:, 20 * (N + 1):20 * (N + 1) + sp.nu]
         self.last_records, self.last_XU, self.last_status, self.last_iters = rec, XU, status, iters
-        if self._wbc is not None:
-            qp, model = self._wbc
-            self.last_wbc = qp.solve(*model(self, self.desired_com(x1, u0, self.t)))
+        self._whole_body(x1, u0)
         hw_next = None if self.hw_measured is None else self._hw_at(self.t + self.rate)
         if push_dv is not None:
             push_dv = torch.as_tensor(push_dv, dtype=torch.float64, device=dev).expand(self.B, 3).contiguous()
@@ -215,9 +236,7 @@ class BatchedRollout:
         x1 = XU[:, 20:40]
         u0 = XU[:, 20 * (N + 1):20 * (N + 1) + sp.nu]
         self.last_records, self.last_XU, self.last_status, self.last_iters = rec, XU, status, iters
-        if self._wbc is not None:                # the consumer of the tick: whole-body QP on the same stream, no host hop
-            qp, model = self._wbc
-            self.last_wbc = qp.solve(*model(self, self.desired_com(x1, u0, self.t)))
+        self._whole_body(x1, u0)
         # plan write-back (:656-675), per instance
         tl = self.t.long()
         if self.update_contact:

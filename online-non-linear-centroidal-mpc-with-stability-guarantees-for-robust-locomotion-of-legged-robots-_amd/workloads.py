@@ -293,27 +293,71 @@ def walk_records(spec, ticks, hw=None, theta_hat=None):
 WBC_ND, WBC_NC = 30, 12           # dofs and contact-wrench dimensions of the whole-body QP (code/inverse_dynamics.py:30-66)
 
 
+WBC_TASK_ROWS = {'lfoot': 6, 'rfoot': 6, 'com': 3, 'torso': 3, 'base': 3}     # the task Jacobians of :46-51
+# position and velocity gains of code/inverse_dynamics.py:43-44 by task (wbc.POS_GAINS / VEL_GAINS: kept here as well, this
+# module is numpy only)
+WBC_POS_GAINS = {'lfoot': 10., 'rfoot': 10., 'com': 5., 'torso': 10., 'base': 10., 'joints': 10.}
+WBC_VEL_GAINS = {'lfoot': 5., 'rfoot': 5., 'com': 10., 'torso': 5., 'base': 3., 'joints': 5.}
+
+
+def _wbc_joint_selection():
+    sel = np.zeros(WBC_ND); sel[18:30] = 1.0                         # "redundant dofs" of the joint task
+    return sel
+
+
+def _wbc_draw(rng, mass, g):
+    """One synthetic robot from `rng`: task Jacobians, target accelerations of the tasks and of the joints, M, h."""
+    Jt = {k: rng.normal(0, 0.4, size=(r, WBC_ND)) for k, r in WBC_TASK_ROWS.items()}
+    for k in ('lfoot', 'rfoot'):
+        Jt[k][:, :6] += np.eye(6)                             # feet move with the floating base
+    Jt['com'][:, 3:6] += np.eye(3)
+    acc = {k: rng.normal(0, 1.0, size=r) for k, r in WBC_TASK_ROWS.items()}
+    acc_joints = rng.normal(0, 1.0, size=WBC_ND)
+    L = rng.normal(0, 0.15, size=(WBC_ND, WBC_ND))
+    Mb = L @ L.T + np.diag(np.concatenate([np.full(3, 2.0), np.full(3, mass), rng.uniform(0.05, 1.0, WBC_ND - 6)]))
+    hb = rng.normal(0, 2.0, size=WBC_ND); hb[5] += mass * g      # gravity on the base translation (z)
+    return Jt, acc, acc_joints, Mb, hb
+
+
 def wbc_synthetic(B, seed=0, contact="ds", mass=HRP4_MASS, g=9.81):
     """Synthetic instances of the size and structure of the reference's QP for HRP-4 (30 dofs): task Jacobians of the
     shapes of :46-51 with random entries, a positive definite mass matrix with the robot's total mass on the base
     translation, gravity on the base, contact Jacobians [.. foot wrench ..] scaled by the contact flags (:109)."""
     rng = np.random.default_rng(seed)
     Hq = np.zeros((B, WBC_ND, WBC_ND)); Fq = np.zeros((B, WBC_ND)); M = np.zeros((B, WBC_ND, WBC_ND)); h = np.zeros((B, WBC_ND)); Jc = np.zeros((B, WBC_NC, WBC_ND))
-    sel = np.zeros(WBC_ND); sel[18:30] = 1.0                         # "redundant dofs" of the joint task
+    sel = _wbc_joint_selection()
     weights = {'lfoot': 1.0, 'rfoot': 1.0, 'com': 1.0, 'torso': 1.0, 'base': 1.0}
-    rows = {'lfoot': 6, 'rfoot': 6, 'com': 3, 'torso': 3, 'base': 3}
+    rows = WBC_TASK_ROWS
     for b in range(B):
-        Jt = {k: rng.normal(0, 0.4, size=(r, WBC_ND)) for k, r in rows.items()}
-        for k in ('lfoot', 'rfoot'):
-            Jt[k][:, :6] += np.eye(6)                             # feet move with the floating base
-        Jt['com'][:, 3:6] += np.eye(3)
+        Jt, acc, acc_joints, Mb, hb = _wbc_draw(rng, mass, g)
         Hb = sum(weights[k] * Jt[k].T @ Jt[k] for k in rows) + 0.1 * np.diag(sel)
-        acc = {k: rng.normal(0, 1.0, size=r) for k, r in rows.items()}
-        Fb = -sum(weights[k] * Jt[k].T @ acc[k] for k in rows) - 0.1 * sel * rng.normal(0, 1.0, size=WBC_ND)
-        L = rng.normal(0, 0.15, size=(WBC_ND, WBC_ND))
-        Mb = L @ L.T + np.diag(np.concatenate([np.full(3, 2.0), np.full(3, mass), rng.uniform(0.05, 1.0, WBC_ND - 6)]))
-        hb = rng.normal(0, 2.0, size=WBC_ND); hb[5] += mass * g      # gravity on the base translation (z)
+        Fb = -sum(weights[k] * Jt[k].T @ acc[k] for k in rows) - 0.1 * sel * acc_joints
         cl, cr = contact in ("ds", "lfoot"), contact in ("ds", "rfoot")
         Jcb = np.vstack([cl * Jt['lfoot'], cr * Jt['rfoot']])
         Hq[b], Fq[b], M[b], h[b], Jc[b] = Hb, Fb, Mb, hb, Jcb
     return Hq, Fq, M, h, Jc
+
+
+def wbc_synthetic_tasks(B, seed=0, mass=HRP4_MASS, g=9.81):
+    """The instances of ``wbc_synthetic(B, seed)`` in the task form of code/inverse_dynamics.py:46-103: J, Jdot (B,21,30),
+    ff, pos_err, vel_err (B,51), qd (B,30), joint_sel (30,), M, h.  The Jacobians, the target accelerations, M and h are
+    wbc_synthetic's own draws (same stream: J[:, :12] is its double-support Jc, bit for bit); Jdot, qd and the errors
+    come from a second generator, and ff = target - k_v e_v - k_p e_p + Jdot qd, so that the commanded accelerations --
+    and with them Hq, Fq -- are wbc_synthetic's up to rounding.  Instance b does not depend on B."""
+    rng, rng2 = np.random.default_rng(seed), np.random.default_rng([seed, 1])
+    NR = sum(WBC_TASK_ROWS.values())
+    J = np.zeros((B, NR, WBC_ND)); Jdot = np.zeros((B, NR, WBC_ND)); qd = np.zeros((B, WBC_ND))
+    ff, pe, ve = (np.zeros((B, NR + WBC_ND)) for _ in range(3))
+    M = np.zeros((B, WBC_ND, WBC_ND)); h = np.zeros((B, WBC_ND))
+    kp = np.concatenate([np.full(r, WBC_POS_GAINS[k]) for k, r in WBC_TASK_ROWS.items()] + [np.full(WBC_ND, WBC_POS_GAINS['joints'])])
+    kv = np.concatenate([np.full(r, WBC_VEL_GAINS[k]) for k, r in WBC_TASK_ROWS.items()] + [np.full(WBC_ND, WBC_VEL_GAINS['joints'])])
+    for b in range(B):
+        Jt, acc, acc_joints, M[b], h[b] = _wbc_draw(rng, mass, g)
+        J[b] = np.vstack([Jt[k] for k in WBC_TASK_ROWS])
+        target = np.concatenate([acc[k] for k in WBC_TASK_ROWS] + [acc_joints])
+        Jdot[b] = rng2.normal(0, 0.4, size=(NR, WBC_ND))
+        qd[b] = rng2.normal(0, 0.5, size=WBC_ND)
+        pe[b] = rng2.normal(0, 0.02, size=NR + WBC_ND)
+        ve[b] = rng2.normal(0, 0.1, size=NR + WBC_ND)
+        ff[b] = target - kv * ve[b] - kp * pe[b] + np.concatenate([Jdot[b] @ qd[b], np.zeros(WBC_ND)])
+    return J, Jdot, ff, pe, ve, qd, _wbc_joint_selection(), M, h
