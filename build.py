@@ -61,9 +61,19 @@ def build_hip_dev(force=False):
 def build_hip_no_reuse(force=False, profile=False):
     """Diagnostic variant (tools/ only; loaded through CMPC_LIB_PATH): -DCMPC_NO_EVAL_REUSE, the one-wave 4-vertex kernel that
     evaluates every stage of a retry pass again -- the third leg of the A/B runs, and with profile=True the `before` of
-    tools/phase_profile.py's retry figures."""
+    tools/phase_profile.py's retry figures.  Built with -DCMPC_SEPARATE_STEP as well: the step applied in the stage load
+    makes a kernel track its failed passes whether it reuses their evaluations or not (it parks and restores the error
+    measures), so without it this would no longer be the kernel that profiles/retry_reuse_* measured as `before`."""
     return _hipcc_lib(os.path.join(ROOT, "tools", "libcmpc_amd_noreuse_prof.so" if profile else "libcmpc_amd_noreuse.so"),
-                      ["CMPC_NO_EVAL_REUSE"] + (["CMPC_PROFILE"] if profile else []), force)
+                      ["CMPC_NO_EVAL_REUSE", "CMPC_SEPARATE_STEP"] + (["CMPC_PROFILE"] if profile else []), force)
+
+
+def build_hip_separate_step(force=False, profile=False):
+    """Diagnostic variant (tools/ only; loaded through CMPC_LIB_PATH): -DCMPC_SEPARATE_STEP, the one-wave 4-vertex kernels that
+    apply the Newton step in a pass of their own (apply_step) instead of where the next matrix sweep loads the iterate -- the
+    other leg of the A/B runs, and with profile=True the `before` of tools/phase_profile.py's step figures."""
+    return _hipcc_lib(os.path.join(ROOT, "tools", "libcmpc_amd_sepstep_prof.so" if profile else "libcmpc_amd_sepstep.so"),
+                      ["CMPC_SEPARATE_STEP"] + (["CMPC_PROFILE"] if profile else []), force)
 
 
 def build_oracle(force=False):
@@ -94,6 +104,13 @@ def build_emu_reuse(force=False, reuse=True):
     reuse=False builds the kernel source with -DCMPC_NO_EVAL_REUSE, the path that evaluates every stage of a retry pass again."""
     return _emu_lib("cmpc_emu_reuse.cpp", "libcmpc_emu_reuse.so" if reuse else "libcmpc_emu_noreuse.so",
                     [] if reuse else ["CMPC_NO_EVAL_REUSE"], force)
+
+
+def build_emu_step(force=False, fused=True):
+    """Host emulation with counters on the step application (tests/emu/cmpc_emu_step.cpp): test harness only.
+    fused=False builds the kernel source with -DCMPC_SEPARATE_STEP, the path that applies the step in a pass of its own."""
+    return _emu_lib("cmpc_emu_step.cpp", "libcmpc_emu_step.so" if fused else "libcmpc_emu_sepstep.so",
+                    [] if fused else ["CMPC_SEPARATE_STEP"], force)
 
 
 def build_device_unit(force=False):
@@ -131,5 +148,7 @@ if __name__ == "__main__":
     print(build_emu_consts(force))
     print(build_emu_reuse(force))
     print(build_emu_reuse(force, reuse=False))
+    print(build_emu_step(force))
+    print(build_emu_step(force, fused=False))
     print(build_device_unit(force))
     print(build_tools(force))

@@ -120,11 +120,19 @@ static __device__ __forceinline__ double cmpc_uniform_d(double v) {
 // two waves meet at workgroup barriers only (CMPC_SYNC_WG: LDS hand-off, CMPC_SYNC_GLOBAL: global memory as well).
 #define CMPC_SYNC_WAVE(w) CMPC_SYNC()
 #define CMPC_FENCE_WAVE(w) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory")
+// "No vector-memory operation of this wave is outstanding", at a point where that is already so at run time: s_waitcnt
+// vmcnt(0) (expcnt and lgkmcnt left at their maxima) as the builtin, which the compiler's own wait insertion reads -- it
+// then plans the waits behind this point from an empty counter.  An asm statement would be opaque to it.
+#define CMPC_VM_LANDED() __builtin_amdgcn_s_waitcnt(0x0F70)
+// a comment line in the kernel's assembly (no instruction): a place a resource test can find
+#define CMPC_ASM_NOTE(text) asm volatile("; " text)
 #endif
 #ifdef CMPC_HOST_EMU
 #define CMPC_SYNC_WAVE(w) emu_barrier_wait(&emu_wave_barrier[(w)])
 #define CMPC_FENCE_WAVE(w) emu_barrier_wait(&emu_wave_barrier[(w)])
 #define CMPC_SYNC_WG() emu_barrier_wait(&emu_barrier)
+#define CMPC_VM_LANDED() do { } while (0)
+#define CMPC_ASM_NOTE(text) do { } while (0)
 #endif
 #ifndef CMPC_RELANE
 #define CMPC_RELANE(x) do { } while (0)
@@ -147,6 +155,15 @@ static_assert(CMPC_CIDX(relax) == CMPC_NCONST - 1 && CMPC_CIDX(box[2]) == 13 && 
 // and the pair reach in different orders and must still form bit for bit alike.  (The host emulation is built with
 // -mfma -ffp-contract=off: the same fused operations, nothing else fused.)
 #define CMPC_FMA(x, y, z) __builtin_fma((x), (y), (z))
+// a + t * b of the Newton step (Solver::step_axpy ...).  On the device ONE rounding, spelled out: the form hipcc's contraction
+// gave apply_step in every kernel, so that the stage load that applies the step (load_stage, STEP_FUSED) agrees with it bit
+// for bit whatever the code around it.  In the host emulation two roundings: it is built with -ffp-contract=off and has
+// always formed the step so -- its answers stay what they were (both of its paths use this one form too).
+#ifdef CMPC_HOST_EMU
+#define CMPC_STEP_MAD(t, b, a) ((a) + (t) * (b))
+#else
+#define CMPC_STEP_MAD(t, b, a) __builtin_fma((t), (b), (a))
+#endif
 #ifndef CMPC_OPAQUE_D
 #define CMPC_OPAQUE_D(x) do { } while (0)
 #endif
@@ -188,6 +205,11 @@ static __device__ __forceinline__ constexpr int cmpc_retry_class(int slot) {
 // retry counters of the test harness (tests/emu/cmpc_emu_reuse.cpp); the profile build's are phase-timer slots
 #ifndef CMPC_RETRY_STAT
 #define CMPC_RETRY_STAT(slot, n) do { } while (0)
+#endif
+// counters of the test harness on the step application (tests/emu/cmpc_emu_step.cpp): 0 stages that took the step in their
+// load, 1 calls of apply_step, 2 stages that took it on the way out of an attempt whose factorisation failed (finish_step)
+#ifndef CMPC_STEP_STAT
+#define CMPC_STEP_STAT(slot, n) do { } while (0)
 #endif
 #define CMPC_NPROF 36
 
@@ -386,6 +408,10 @@ template <bool PIPE> struct LdsMap<4, 1, PIPE> : Sizes<4, 1> {
   static constexpr int oRED = oPC + S::NXA;
   static constexpr int oCOLD = oRED + 4;
   static constexpr int oDUMP = oCOLD + 8;
+  // The Newton step the next matrix sweep applies where it loads the iterate (Solver::STEP_FUSED), in words the map has to
+  // spare: the two step lengths in the twentieth word of the two record rows (19 are staged), "a step is pending" in the
+  // fourth reduction word (the one-wave solver uses three: stage_ineq).
+  static constexpr int oSTEP_AP = oSR + 19, oSTEP_AD = oSRP + 19, oSTEP_ON = oRED + 3;
   // from the stage's loads to its gradient
   static constexpr int oXK = oDUMP + DUMPN + ((oDUMP + DUMPN) & 1);
   static constexpr int oUK = oXK + S::NXA;
@@ -540,7 +566,15 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
   // across the retry loop -- and spilled
   static constexpr int ER_AT = 256;
   static_assert(!RETRY_TRACK_POSSIBLE || (ER_AT >= 3 * NZ + NXA + 3 * NF && ER_AT + 6 * WS <= D::NTRI), "the parked error measures fit the M region");
-  static constexpr bool RETRY_TRACK = EVAL_REUSE || (CMPC_RETRY_TRACK && NV == 4 && NW == 1 && !PIPE && !GAIN);
+  // The Newton step is applied by the matrix sweep that follows it, where load_stage reads the iterate anyway, instead of
+  // in a pass of its own between two full fences (apply_step): see load_stage.  -DCMPC_SEPARATE_STEP builds the kernel
+  // with the separate pass.
+#ifdef CMPC_SEPARATE_STEP
+  static constexpr bool STEP_FUSED = false;
+#else
+  static constexpr bool STEP_FUSED = RETRY_TRACK_POSSIBLE;
+#endif
+  static constexpr bool RETRY_TRACK = EVAL_REUSE || STEP_FUSED || (CMPC_RETRY_TRACK && NV == 4 && NW == 1 && !PIPE && !GAIN);
 
   const KArgs &ka;
   const cmpc_spec &sp;
@@ -627,28 +661,85 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
     vx = cx[j]; vy = cy[j];
   }
 
+  // The Newton step on one word of the iterate: the one set of expressions of apply_step and of the stage load that
+  // applies the step on the way (load_stage, STEP_FUSED).  The multiply-adds are CMPC_STEP_MAD: on the device single
+  // roundings, spelled out -- the form hipcc's contraction gave apply_step's a + ap * b in every kernel; the two places
+  // must agree bit for bit whatever it would choose around them (the divisions are correctly rounded either way).
+  CMPC_DEV static double step_axpy(double a, double t, double b) { return CMPC_STEP_MAD(t, b, a); }            // a + t b
+  CMPC_DEV static double step_toward(double c, double t, double d) { return CMPC_STEP_MAD(t, d - c, c); }      // c + t (d - c)
+  // slack and multiplier of a row that carries one (z != 0: the caller's test); the multiplier stays within 1e10 of mu / s
+  CMPC_DEV static void step_slack(double &s, double &z, double ds, double dz, double ap, double ad, double mu) {
+    s = CMPC_STEP_MAD(ap, ds, s);
+    const double zn = CMPC_STEP_MAD(ad, dz, z);
+    const double lo = mu / s / 1e10, hi = mu / s * 1e10;
+    z = fmin(fmax(zn, lo), hi);
+  }
+
   // ---------------------------------------------------------------------------------------
   // Stage loads: x_k, u_k, x_{k+1}, lam_k, lam_{k+1}, s_k, z_k, uprox_k and the record rows.
   // ---------------------------------------------------------------------------------------
   // Stage iterates and record rows to LDS.  Every global load is issued unconditionally (clamped
   // indices) before the first LDS write: loads inside lane- or stage-conditional blocks compile to
   // one exposed HBM round trip each (load, s_waitcnt vmcnt(0), ds_write), a dozen per stage.
-  CMPC_DEV void load_stage(int k) {
+  // STEP_FUSED, first = the first visit of stage k in this iteration, with a step pending (D::oSTEP_ON, wave-uniform): the
+  // Newton step of the last iteration is applied to the words of node k as they arrive -- x_k, lam_k, u_k, s_k, z_k, with
+  // step_axpy / step_toward / step_slack (apply_step's expressions) -- and the new values are what goes to LDS and back
+  // to the iterate arrays, which the forward sweep, write_solution / write_state and a retry pass read.  x_{k+1} and lam_{k+1} took their step at stage
+  // k + 1's load, in this lane: read plain.  A real branch, not a step of length zero: with no step pending (the first
+  // iteration of an attempt) the direction arrays hold whatever the memory held.
+  CMPC_DEV void load_stage(int k, bool first = false, double mu = 0.0) {
     static_assert(NXA <= 64 && NU <= 64, "one lane per state / input component");
     constexpr int NIH = (NI + WS - 1) / WS;
     const bool in = k < N;
     const int kn = in ? k + 1 : k, ku = in ? k : N - 1, kp = (k >= 1) ? k - 1 : 0;
     const int ix = (lane < NXA) ? lane : 0, iu = (lane < NU) ? lane : 0, ir = (lane < 19) ? lane : 0;
-    const double x0 = gx[k * NXA + ix], x1 = gx[kn * NXA + ix];
-    const double u0 = gu[ku * NU + iu], up = gupx[ku * NU + iu];
+    bool step = false;
+    if constexpr (STEP_FUSED) { if (first) step = CMPC_UNIFORM_INT((int)(L(D::oSTEP_ON) != 0.0)) != 0; }
+    // (the five direction words ahead of the stage's own, in the same batch of loads: one round trip)
+    double dxv = 0.0, lnv = 0.0, duv = 0.0, dsv[NIH], dzv[NIH];
+#pragma unroll
+    for (int h = 0; h < NIH; ++h) { dsv[h] = 0.0; dzv[h] = 0.0; }
+    if constexpr (STEP_FUSED) {
+      if (step) {
+        dxv = gdx[k * NXA + ix]; lnv = glamn[k * NXA + ix]; duv = gdu[ku * NU + iu];
+#pragma unroll
+        for (int h = 0; h < NIH; ++h) {
+          const int r = lane + WS * h, rc = (r < NI) ? r : 0;
+          dsv[h] = gds[k * NI + rc]; dzv[h] = gdz[k * NI + rc];
+        }
+      }
+    }
+    double x0 = gx[k * NXA + ix];
+    const double x1 = gx[kn * NXA + ix];
+    double u0 = gu[ku * NU + iu];
+    const double up = gupx[ku * NU + iu];
     const double r0 = rec[24 + 19 * ku + ir], r1 = rec[24 + 19 * kp + ir], hd = rec[(lane < 24) ? lane : 0];
     double sv[NIH], zv[NIH];
-    const double l0 = glam[k * NXA + ix], l1 = glam[kn * NXA + ix];
+    double l0 = glam[k * NXA + ix];
+    const double l1 = glam[kn * NXA + ix];
     {
 #pragma unroll
       for (int h = 0; h < NIH; ++h) {
         const int r = lane + WS * h, rc = (r < NI) ? r : 0;
         sv[h] = gsl[k * NI + rc]; zv[h] = gz[k * NI + rc];
+      }
+    }
+    if constexpr (STEP_FUSED) {
+      if (step) {
+        const double ap = L(D::oSTEP_AP), ad = L(D::oSTEP_AD);
+        // (node 0: x_0 is data and lam_0 is not part of the step; the terminal node has no inputs -- `u0` is u_{N-1} there)
+        if (k >= 1) { x0 = step_axpy(x0, ap, dxv); l0 = step_toward(l0, ap, lnv); }
+        if (in) u0 = step_axpy(u0, ap, duv);
+#pragma unroll
+        for (int h = 0; h < NIH; ++h) {
+          // (a row without a multiplier keeps its words: by selects -- as a branch over the lanes, the loads of ds and dz
+          // sink into it, a round trip of their own)
+          double sn = sv[h], zn = zv[h];
+          step_slack(sn, zn, dsv[h], dzv[h], ap, ad, mu);
+          const bool on = zv[h] != 0.0;
+          sv[h] = on ? sn : sv[h]; zv[h] = on ? zn : zv[h];
+        }
+        CMPC_STEP_STAT(0, 1);
       }
     }
     if (lane < NXA) {
@@ -666,6 +757,26 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
     if (lane < 19) { L(D::oSR + lane) = in ? r0 : 0.0; L(D::oSRP + lane) = (k >= 1) ? r1 : 0.0; }
     if (lane < 24) L(D::oHDR + lane) = hd;
     sync();
+    if constexpr (STEP_FUSED) {
+      // Every load of the stage has landed: the LDS commit above consumed the last of them, and the counter is in order.
+      // The compiler cannot know it -- it must allow for a commit block that no lane enters, which leaves its loads
+      // pending -- and would put counted waits for those loads between the stores below and at the join behind them, where
+      // at run time they wait for the stores' acknowledgements (the counter counts stores too), one round trip after another
+      // in the stage's critical path.  Said here, on both paths, it costs nothing and the stores issue back to back; the
+      // first wait behind them is that of the stage's next loads, which are in flight by then.
+      CMPC_VM_LANDED();
+      // (Rows without a multiplier store the words they loaded.)
+      if (step) {
+        CMPC_ASM_NOTE("cmpc: the step's stores");   // (tests/test_step_fusion_resources.py reads the waits from here on)
+        if (k >= 1 && lane < NXA) { gx[k * NXA + lane] = x0; glam[k * NXA + lane] = l0; }
+        if (in && lane < NU) gu[k * NU + lane] = u0;
+#pragma unroll
+        for (int h = 0; h < NIH; ++h) {
+          const int r = lane + WS * h;
+          if (r < NI) { gsl[k * NI + r] = sv[h]; gz[k * NI + r] = zv[h]; }
+        }
+      }
+    }
   }
 
   // ---------------------------------------------------------------------------------------
@@ -1772,7 +1883,7 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
       const int cz = (lane < NZ) ? lane : 0, ci = (lane < NI) ? lane : 0;
       re_al = sk[D::gAL + cz]; re_w0 = sk[re + D::rW0 + ci]; re_h0 = sk[re + D::rH0 + cz]; re_h1 = sk[re + D::rH1 + cz];
     }
-    load_stage(k);
+    load_stage(k, !reuse_, mu);                // (reuse_: a failed pass of this iteration has been here, and applied the step)
     CMPC_TICK(24);
     const GArr st = stage(k);
     if (reuse) {
@@ -2073,8 +2184,11 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
         if constexpr (RETRY_TRACK) {
           const bool done = k >= k_done;         // (wave-uniform: both are)
           CMPC_RETRY_MARK(done);
-          if (EVAL_REUSE || !done) eval_stage(k, mu, reg, wz, x0n2, er, init, done);
-          else { Err again = er; eval_stage(k, mu, reg, wz, x0n2, again, init); }   // (profile build of the old path: same measures either way)
+          if constexpr (EVAL_REUSE) eval_stage(k, mu, reg, wz, x0n2, er, init, done);
+          else {                                 // (the path without reuse evaluates the stage again: same measures either way)
+            Err again = er;
+            eval_stage(k, mu, reg, wz, x0n2, done ? again : er, init, done);
+          }
           if (!riccati_stage(k)) {
             CMPC_RETRY_MARK(false);
             if (!init) { CMPC_RETRY_STAT(29, N + 1 - k); if (k < k_done) k_done = CMPC_UNIFORM_INT(k); }
@@ -2490,6 +2604,7 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
   }
 
   CMPC_DEV void apply_step(double mu, double ap, double ad) {
+    CMPC_STEP_STAT(1, 1);
     gsync();                                  // directions were written with a per-stage lane mapping
     // elementwise updates, four independent load groups in flight per pass
     constexpr int UF = 4;
@@ -2505,7 +2620,7 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
 #pragma unroll
       for (int q = 0; q < UF; ++q) {
         const int e = e0 + lane + WS * q;
-        if (e < (N + 1) * NXA) { gx[e] = a[q] + ap * b[q]; glam[e] = c[q] + ap * (d[q] - c[q]); }
+        if (e < (N + 1) * NXA) { gx[e] = step_axpy(a[q], ap, b[q]); glam[e] = step_toward(c[q], ap, d[q]); }
       }
     }
     if (do_xu)
@@ -2519,7 +2634,7 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
 #pragma unroll
       for (int q = 0; q < UF; ++q) {
         const int e = e0 + lane + WS * q;
-        if (e < N * NU) gu[e] = a[q] + ap * b[q];
+        if (e < N * NU) gu[e] = step_axpy(a[q], ap, b[q]);
       }
     }
     if (do_sz)
@@ -2534,13 +2649,21 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
       for (int q = 0; q < UF; ++q) {
         const int e = e0 + lane + WS * q;
         if (e < (N + 1) * NI && zq[q] != 0.0) {
-          const double s = sq[q] + ap * dsq[q];
-          const double z = zq[q] + ad * dzq[q];
-          const double lo = mu / s / 1e10, hi = mu / s * 1e10;
-          gsl[e] = s; gz[e] = fmin(fmax(z, lo), hi);
+          double s = sq[q], z = zq[q];
+          step_slack(s, z, dsq[q], dzq[q], ap, ad, mu);
+          gsl[e] = s; gz[e] = z;
         }
       }
     }
+    gsync();
+  }
+
+  // STEP_FUSED: the matrix sweep has failed for every regularisation (or was never run: CMPC_TEST_FAIL_ITER) and the
+  // attempt ends.  Its passes have applied the pending step at the stages they visited, k_done .. N; the others take it
+  // here, so that the iterate arrays are what apply_step would have left -- write_solution reads them next.
+  CMPC_DEV void finish_step(double mu, int k_done) {
+    if (CMPC_UNIFORM_INT((int)(L(D::oSTEP_ON) != 0.0)) == 0) return;   // (the first iteration of an attempt: no step to finish)
+    for (int k = k_done - 1; k >= 0; --k) { load_stage(k, true, mu); CMPC_STEP_STAT(2, 1); }
     gsync();
   }
 
@@ -2609,7 +2732,8 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
   }
 
   // X (20 x (N+1)) then U (nu x N), the reference's layout.  Reads the iterate arrays as apply_step /
-  // initial_point left them (both end with a full fence).
+  // initial_point left them (both end with a full fence) -- STEP_FUSED: as the matrix sweep's stage loads left them, behind
+  // the fence the caller puts in front.
   CMPC_DEV void write_solution(double *out_) {
     const GArr out{out_};
     for (int e = lane; e < (N + 1) * CMPC_NX; e += WS) out[e] = gx[(e / CMPC_NX) * NXA + (e % CMPC_NX)];
@@ -2859,6 +2983,7 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
       reg_last = zero; kkt_best = inf; snapped = zero;
       if (!carry) kkt_saved = inf;
       if constexpr (CNT_LDS) { R(D::oCOLD + 4) = zero; R(D::oCOLD + 5) = zero; R(D::oCOLD + 6) = zero - 1.0; R(D::oCOLD + 7) = zero; }
+      if constexpr (STEP_FUSED) L(D::oSTEP_ON) = zero;          // no step is pending
     }
     // acceptable level; every iterate the acceptable-level counter counts is also saved (see the oracle).  Formed
     // where they are used (two instructions) instead of being kept live across the solve.
@@ -2887,7 +3012,11 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
         else reg *= (rl == 0.0) ? 100.0 : 8.0;
         if (reg > 1e20) { fail = true; break; }
       }
-      if (fail) { st = CMPC_NUMERICAL | NOSTEP; break; }
+      if (fail) {
+        if constexpr (STEP_FUSED) finish_step(mu, k_done);
+        st = CMPC_NUMERICAL | NOSTEP; break;
+      }
+      if constexpr (STEP_FUSED) L(D::oSTEP_ON) = 0.0;           // every stage has taken the step (load_stage ends with a barrier)
 #ifdef CMPC_DEBUG_FIRST_SWEEP                  // (diagnostic build, tools/slab_diff.py: leave the slab as the first matrix sweep wrote it)
       if (it == 0) break;
 #endif
@@ -2922,6 +3051,7 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
       if (polish < 0) {
         // best acceptable iterate so far (see the oracle): whatever ends the run, it is what is returned
         if (kkt <= save_tol() && kkt < ks) {
+          if constexpr (STEP_FUSED) gsync();    // (the sweep stored the iterate with its own lane mapping)
           if (!PIPE || wv == 0) write_solution(out);
           if constexpr (GAIN) { if (!PIPE || wv == 0) write_state(gbuf.p, mu); }   // (the whole saved iterate)
           ks = kkt; kkt_saved = kkt;
@@ -2995,8 +3125,13 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
         vector_sweeps(mu, mu - mu_sweep, ap, ad);
         CMPC_TICK(6);
         count_stall();
-        apply_step(mu, ap, ad);
-        CMPC_TICK(7);
+        if constexpr (STEP_FUSED) {
+          // (the next iteration's matrix sweep applies the step, stage by stage, at the barrier value it is called with: this mu)
+          L(D::oSTEP_AP) = ap; L(D::oSTEP_AD) = ad; L(D::oSTEP_ON) = 1.0;
+        } else {
+          apply_step(mu, ap, ad);
+          CMPC_TICK(7);
+        }
       }
     }
     bool use_saved = (st & SAVED) != 0;
@@ -3012,6 +3147,7 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
     if (nostep && ks_end <= acc_tol()) { st = CMPC_ACCEPTABLE; kkt = ks_end; use_saved = true; }
     const bool keep = resume && (st == CMPC_MAX_ITER || st == CMPC_NUMERICAL) && ks_end <= acc_tol();
     if (keep && !(it < sp.max_iter)) { st = CMPC_ACCEPTABLE; kkt = ks_end; use_saved = true; }
+    if constexpr (STEP_FUSED) { if (!use_saved && !keep) gsync(); }   // (the last sweep stored the iterate with its own lane mapping)
     if (!use_saved && !keep && (!PIPE || wv == 0)) write_solution(out);
     if constexpr (GAIN) ret_saved = use_saved;
     // (the verdict is the same in every lane; said so, the attempt loop is a uniform loop and what it carries -- the
