@@ -99,6 +99,11 @@ def build_emu_consts(force=False):
     return _emu_lib("cmpc_emu_consts.cpp", "libcmpc_emu_consts.so", force=force)
 
 
+def build_emu_gain_consts(force=False):
+    """Host emulation of the gain variant with per-instance constants (tests/emu/cmpc_emu_gain_consts.cpp): test harness only."""
+    return _emu_lib("cmpc_emu_gain_consts.cpp", "libcmpc_emu_gain_consts.so", force=force)
+
+
 def build_emu_reuse(force=False, reuse=True):
     """Host emulation with counters on the retried factorisations (tests/emu/cmpc_emu_reuse.cpp): test harness only.
     reuse=False builds the kernel source with -DCMPC_NO_EVAL_REUSE, the path that evaluates every stage of a retry pass again."""
@@ -146,6 +151,7 @@ if __name__ == "__main__":
     print(build_emu(force))
     print(build_emu_gain(force))
     print(build_emu_consts(force))
+    print(build_emu_gain_consts(force))
     print(build_emu_reuse(force))
     print(build_emu_reuse(force, reuse=False))
     print(build_emu_step(force))

@@ -187,6 +187,42 @@ int cmpc_solve_batch_consts(cmpc_handle *h, int32_t B, const double *params, con
                             const double *state_in, double *out_XU, double *state_out, int32_t *status, int32_t *iters,
                             double *kkt_res, void *stream);
 
+/*
+ * cmpc_solve_batch_consts plus the first-stage feedback gain of every instance, taken with that instance's own constants:
+ * the gains of a mixed fleet (nominal, payload, mpc_rate 10) in ONE launch.
+ *   consts  as for cmpc_solve_batch_consts, NOT NULL (a caller with the handle's constants calls cmpc_solve_batch_gain)
+ *   gain    as for cmpc_solve_batch_gain,   NOT NULL (a caller who wants no gain calls cmpc_solve_batch_consts)
+ * out_XU, status, iters, kkt_res and state_out are bit for bit those of cmpc_solve_batch_consts; with rows equal to
+ * cmpc_spec_consts(spec) the gain is bit for bit that of cmpc_solve_batch_gain.  An instance whose row is refused returns as
+ * cmpc_solve_batch_consts says and its whole gain block is NaN; the other instances are untouched.  The "gain_consts"
+ * variant of the kernel runs (e.g. "cmpc_solve_gain_consts_kernel<4, 1>").  The saved iterates are those of
+ * cmpc_solve_batch_gain (one allocation per handle, made by the first call of either: it synchronises the device and must
+ * not be made under stream capture).
+ */
+int cmpc_solve_batch_gain_consts(cmpc_handle *h, int32_t B, const double *params, const double *consts, const double *warm_XU,
+                                 const double *state_in, double *out_XU, double *state_out, int32_t *status, int32_t *iters,
+                                 double *kkt_res, double *gain, void *stream);
+
+/*
+ * The gain applied between two solves, one launch for the batch:
+ *   params  [B][CMPC_NREC(N)]     the records the gains were taken at; only x0 = params[b][0:20] is read
+ *   XU      [B][CMPC_NSOL(N,nv)]  the solutions: x_1 = X[:,1], u_0 = U[:,0]
+ *   gain    [B][CMPC_NGAIN(nv)]   from cmpc_solve_batch_gain / _gain_consts
+ *   x_meas  [B][20]               the measured state, in the layout of x0
+ *   columns                       bit c set: column c of the gain is used; bits 20..31 must be 0 (the call fails).
+ *                                 0xFFF = the centroidal state (CoM, velocity, angular momentum, theta_hat)
+ *   x1_out [B][20], u0_out [B][nu], used [B] (one byte per instance)
+ * With dx[c] = x_meas[b][c] - x0[c] on the chosen columns and 0 elsewhere:
+ *   x1_out[b] = x_1 + G[0:20] dx,   u0_out[b] = u_0 + G[20:] dx,   used[b] = 1.
+ * An instance HOLDS -- x1_out[b] = x_1 and u0_out[b] = u_0 copied bit for bit, used[b] = 0 -- when any of the (20 + nu) x 20
+ * words of gain[b] is not finite (a solve without a gain leaves the whole block NaN) or a chosen word of x_meas[b] or of
+ * x0 is not finite; words of x_meas outside `columns` are not read.  No handle, no allocation, no synchronisation: all
+ * pointers are device memory of the current HIP device, the launch is asynchronous on `stream` and may be captured.
+ * The outputs must not overlap the inputs.
+ */
+int cmpc_gain_track(int32_t N, int32_t nv, int32_t B, const double *params, const double *XU, const double *gain,
+                    const double *x_meas, uint32_t columns, double *x1_out, double *u0_out, uint8_t *used, void *stream);
+
 /* Average kernel time (ms) of the last cmpc_solve_batch on this handle, measured with
  * HIP events on the launch stream; synchronises that stream. */
 int cmpc_last_kernel_ms(cmpc_handle *h, float *ms);

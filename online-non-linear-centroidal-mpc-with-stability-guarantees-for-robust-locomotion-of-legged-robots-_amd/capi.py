@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("CMPC_LIB_PATH") or os.path.join(_HERE, "libcmpc_amd.s
 #: every symbol include/cmpc.h declares
 SYMBOLS = ("cmpc_default_spec", "cmpc_create", "cmpc_destroy", "cmpc_workspace_bytes",
            "cmpc_solve_batch", "cmpc_solve_batch_state", "cmpc_solve_batch_gain", "cmpc_solve_batch_consts", "cmpc_spec_consts",
+           "cmpc_solve_batch_gain_consts", "cmpc_gain_track",
            "cmpc_last_kernel_ms", "cmpc_last_kernel_name", "cmpc_last_error",
            "cmpc_version",
            "cmpc_tables_create", "cmpc_tables_destroy", "cmpc_build_records",
@@ -61,6 +62,10 @@ def load():
     lib.cmpc_solve_batch_gain.restype = ctypes.c_int
     lib.cmpc_solve_batch_consts.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cmpc_solve_batch_consts.restype = ctypes.c_int
+    lib.cmpc_solve_batch_gain_consts.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.cmpc_solve_batch_gain_consts.restype = ctypes.c_int
+    lib.cmpc_gain_track.argtypes = [i32, i32, i32, vp, vp, vp, vp, ctypes.c_uint32, vp, vp, vp, vp]
+    lib.cmpc_gain_track.restype = ctypes.c_int
     lib.cmpc_spec_consts.argtypes = [c_spec_p, ctypes.POINTER(ctypes.c_double)]
     lib.cmpc_spec_consts.restype = None
     lib.cmpc_last_kernel_ms.argtypes = [vp, ctypes.POINTER(ctypes.c_float)]

@@ -196,6 +196,23 @@ __global__ void __launch_bounds__(128, WPS) cmpc_solve_pair_consts_kernel(cmpc::
   cmpc_instance_loop<NV, 1, true, false, true>(ka, nullptr, nullptr, consts, ticket, order);
 }
 
+// Gain and per-instance constants together (cmpc_solve_batch_gain_consts): Solver<..., GAIN = true, CONSTS = true> -- the gain
+// is taken with the instance's own row, and a refused row has a gain block of NaN (Solver::reject).  Kernels of their own
+// again: the nine above compile to what they compiled to without these.
+template <int NV, int NW>
+__global__ void __launch_bounds__(64 * NW, (NV == 4 ? CMPC_WAVES_PER_SIMD : 1)) cmpc_solve_gain_consts_kernel(cmpc::KArgs ka, double *gain, double *gbuf,
+                                                                                                               const double *__restrict__ consts,
+                                                                                                               int *ticket, const int *__restrict__ order) {
+  cmpc_instance_loop<NV, NW, false, true, true>(ka, gain, gbuf, consts, ticket, order);
+}
+
+template <int NV, int WPS>
+__global__ void __launch_bounds__(128, WPS) cmpc_solve_pair_gain_consts_kernel(cmpc::KArgs ka, double *gain, double *gbuf,
+                                                                               const double *__restrict__ consts, int *ticket,
+                                                                               const int *__restrict__ order) {
+  cmpc_instance_loop<NV, 1, true, true, true>(ka, gain, gbuf, consts, ticket, order);
+}
+
 // One workgroup per record (grid-stride over the batch), one lane per pair of output words: each
 // lane assembles two consecutive doubles and issues one 16-byte store, so a wavefront writes 1 KiB of
 // contiguous record per instruction; reads are gathers from tables that stay L2-resident
@@ -344,6 +361,78 @@ __global__ void __launch_bounds__(256) cmpc_rollout_advance_kernel(
       }
     }
     __syncthreads();                                                     // (grid-stride: the next instance's reads follow these writes)
+  }
+}
+
+// The gain between two solves (include/cmpc.h, cmpc_gain_track): x_1 + G_x dx and u_0 + G_u dx, dx = x_meas - x0 on the chosen
+// columns, or x_1 and u_0 as they stand when the gain cannot be used.  One wave per instance, TRACK_WAVES instances per
+// workgroup, grid-stride.  HBM-bound on G ((20 + nu) x 20 doubles, read once): the block is read as consecutive 16-byte
+// pairs, lane l of the wave the pairs l, l + 64, ... -- 1 KiB contiguous per load instruction, all loads issued before the
+// first is used.  A pair lies within one row of G (20 is even); its two products go to the wave's LDS tile, and the lane of
+// a row adds the row's ten pairs in their order.  "Any word not finite" is a flag per lane and a ballot over the wave (not
+// a maximum: fmax drops NaNs).  Every wave touches its own slice of the tile only; the barriers order its lanes.
+constexpr int TRACK_WAVES = 4;
+template <int NV>
+__global__ void __launch_bounds__(64 * TRACK_WAVES) cmpc_gain_track_kernel(
+    int B, int nrec, int nsol, int u_at, const double *__restrict__ params, const double *__restrict__ XU,
+    const double *__restrict__ gain, const double *__restrict__ x_meas, unsigned columns, int aligned,
+    double *__restrict__ x1_out, double *__restrict__ u0_out, unsigned char *__restrict__ used) {
+  constexpr int NU = CMPC_NU(NV), ROWS = CMPC_NX + NU, RP = CMPC_NX / 2, NP = ROWS * RP, IT = (NP + 63) / 64;
+  static_assert(CMPC_NX % 2 == 0 && 2 * NP == CMPC_NGAIN(NV), "a 16-byte pair stays within one row of the gain");
+  __shared__ __attribute__((aligned(16))) double part[TRACK_WAVES][NP];
+  __shared__ __attribute__((aligned(16))) double dxs[TRACK_WAVES][CMPC_NX];
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int b0 = blockIdx.x * TRACK_WAVES; b0 < B; b0 += gridDim.x * TRACK_WAVES) {   // (b0: the same in every wave of the workgroup)
+    const int b = b0 + w;
+    const bool on = b < B;
+    double2 g[IT];
+    bool bad = false;
+    if (on) {
+      const double *G = gain + (size_t)b * CMPC_NGAIN(NV);
+#pragma unroll
+      for (int i = 0; i < IT; ++i) {
+        const int q = lane + 64 * i;
+        g[i] = make_double2(0.0, 0.0);
+        if (q < NP) g[i] = aligned ? *reinterpret_cast<const double2 *>(G + 2 * q) : make_double2(G[2 * q], G[2 * q + 1]);
+      }
+      if (lane < CMPC_NX) {
+        double d = 0.0;
+        if ((columns >> lane) & 1u) {
+          const double xm = x_meas[(size_t)b * CMPC_NX + lane], x0 = params[(size_t)b * nrec + lane];
+          bad = !(fabs(xm) < INFINITY) || !(fabs(x0) < INFINITY);
+          d = xm - x0;
+        }
+        dxs[w][lane] = d;
+      }
+    }
+    __syncthreads();
+    if (on) {
+#pragma unroll
+      for (int i = 0; i < IT; ++i) {
+        const int q = lane + 64 * i;
+        if (q < NP) {
+          const int c = 2 * (q % RP);
+          bad = bad || !(fabs(g[i].x) < INFINITY) || !(fabs(g[i].y) < INFINITY);
+          part[w][q] = g[i].x * dxs[w][c] + g[i].y * dxs[w][c + 1];
+        }
+      }
+    }
+    const bool hold = __ballot(bad) != 0;                               // (the wave's own lanes: one instance)
+    __syncthreads();
+    if (on) {
+      for (int r = lane; r < ROWS; r += 64) {
+        double acc = 0.0;
+#pragma unroll
+        for (int j = 0; j < RP; ++j) acc += part[w][RP * r + j];
+        const double base = XU[(size_t)b * nsol + (r < CMPC_NX ? CMPC_NX + r : u_at + r - CMPC_NX)];
+        const double v = hold ? base : base + acc;
+        if (r < CMPC_NX) x1_out[(size_t)b * CMPC_NX + r] = v;
+        else u0_out[(size_t)b * NU + r - CMPC_NX] = v;
+      }
+      if (lane == 0) used[b] = hold ? 0 : 1;
+    }
+    // (no barrier here: the next instance's dxs are written behind the second barrier above, which every read of them
+    // precedes, and its part behind its own first barrier, which these reads precede)
   }
 }
 
@@ -561,14 +650,14 @@ int cmpc_solve_batch(cmpc_handle *h, int32_t B, const double *params, const doub
 
 }  // extern "C"
 
-// The solver kernels: what cmpc_solve_batch_state, _gain and _consts launch (rows; never gain and consts both: there is no
-// gain variant with per-instance constants), by shape (columns): the pipelined pair, the one-wave 4-vertex kernel, the
+// The solver kernels: what cmpc_solve_batch_state, _gain, _consts and _gain_consts launch (rows: without either, with a gain,
+// with per-instance constants, with both), by shape (columns): the pipelined pair, the one-wave 4-vertex kernel, the
 // 8-vertex one and -- developer build -- the pair built for one wave per SIMD.  name: what cmpc_last_kernel_name reports.
 struct SolverKernel { const void *fn; int block; const char *name; };
-enum { VARIANT_PLAIN, VARIANT_GAIN, VARIANT_CONSTS };
+enum { VARIANT_PLAIN, VARIANT_GAIN, VARIANT_CONSTS, VARIANT_GAIN_CONSTS };
 enum { SHAPE_PAIR, SHAPE_NV4, SHAPE_NV8, SHAPE_PAIR_WPS1 };
 static_assert(cmpc::WAVES_NV8 == 2, "the names of the 8-vertex kernels");
-static const SolverKernel solver_kernels[3][4] = {
+static const SolverKernel solver_kernels[4][4] = {
     {{(const void *)cmpc_solve_pair_kernel<4, 2>, 128, "cmpc_solve_pair_kernel<4, 2>"},
      {(const void *)cmpc_solve_kernel<4, 1>, 64, "cmpc_solve_kernel<4, 1>"},
      {(const void *)cmpc_solve_kernel<8, cmpc::WAVES_NV8>, 64 * cmpc::WAVES_NV8, "cmpc_solve_kernel<8, 2>"},
@@ -590,10 +679,17 @@ static const SolverKernel solver_kernels[3][4] = {
      {(const void *)cmpc_solve_pair_consts_kernel<4, 1>, 128, "cmpc_solve_pair_consts_kernel<4, 1>"},
 #endif
     },
+    {{(const void *)cmpc_solve_pair_gain_consts_kernel<4, 2>, 128, "cmpc_solve_pair_gain_consts_kernel<4, 2>"},
+     {(const void *)cmpc_solve_gain_consts_kernel<4, 1>, 64, "cmpc_solve_gain_consts_kernel<4, 1>"},
+     {(const void *)cmpc_solve_gain_consts_kernel<8, cmpc::WAVES_NV8>, 64 * cmpc::WAVES_NV8, "cmpc_solve_gain_consts_kernel<8, 2>"},
+#ifdef CMPC_DEV_KNOBS
+     {(const void *)cmpc_solve_pair_gain_consts_kernel<4, 1>, 128, "cmpc_solve_pair_gain_consts_kernel<4, 1>"},
+#endif
+    },
 };
 
-// cmpc_solve_batch_state, cmpc_solve_batch_gain and cmpc_solve_batch_consts: gain == nullptr and consts == nullptr launch the
-// plain kernels
+// cmpc_solve_batch_state, cmpc_solve_batch_gain, cmpc_solve_batch_consts and cmpc_solve_batch_gain_consts: gain == nullptr and
+// consts == nullptr launch the plain kernels
 static int solve_batch(cmpc_handle *h, int32_t B, const double *params, const double *warm_XU, const double *state_in,
                        double *out_XU, double *state_out, int32_t *status, int32_t *iters, double *kkt_res, double *gain,
                        const double *consts, void *stream) {
@@ -638,14 +734,27 @@ static int solve_batch(cmpc_handle *h, int32_t B, const double *params, const do
 #ifdef CMPC_DEV_KNOBS
   if (pair && h->pair_per_cu < 3) shape = SHAPE_PAIR_WPS1;
 #endif
-  const SolverKernel &k = solver_kernels[gain ? VARIANT_GAIN : consts ? VARIANT_CONSTS : VARIANT_PLAIN][shape];
+  const int variant = (gain && consts) ? VARIANT_GAIN_CONSTS : gain ? VARIANT_GAIN : consts ? VARIANT_CONSTS : VARIANT_PLAIN;
+  const SolverKernel &k = solver_kernels[variant][shape];
   void *args_plain[] = {&ka, &h->ticket, &h->order}, *args_gain[] = {&ka, &gain, &h->gbuf, &h->ticket, &h->order},
-       *args_consts[] = {&ka, &consts, &h->ticket, &h->order};
+       *args_consts[] = {&ka, &consts, &h->ticket, &h->order},
+       *args_gain_consts[] = {&ka, &gain, &h->gbuf, &consts, &h->ticket, &h->order};
+  void **args[] = {args_plain, args_gain, args_consts, args_gain_consts};
   h->last_kernel = k.name;
-  HIP_TRY(h, hipLaunchKernel(k.fn, dim3(grid), dim3(k.block), gain ? args_gain : consts ? args_consts : args_plain, 0, st));
+  HIP_TRY(h, hipLaunchKernel(k.fn, dim3(grid), dim3(k.block), args[variant], 0, st));
   HIP_TRY(h, hipGetLastError());
   HIP_TRY(h, hipEventRecord(h->ev1, st));
   h->timed = true;
+  return 0;
+}
+
+// The saved iterate of every slab, which the gain kernels need (with and without per-instance constants: one allocation):
+// made by the first gain call on the handle; hipMalloc synchronises the device.  who: the entry point, for the message.
+static int gbuf_ready(cmpc_handle *h, const char *who) {
+  if (h->gbuf) return 0;
+  DeviceGuard guard(h->device);
+  if (!guard.ok) return fail(h, std::string(who) + ": cannot select the handle's device");
+  HIP_TRY(h, hipMalloc(&h->gbuf, (size_t)h->slabs * CMPC_NSTATE(h->spec.N, h->spec.nv) * sizeof(double)));
   return 0;
 }
 
@@ -675,12 +784,35 @@ int cmpc_solve_batch_gain(cmpc_handle *h, int32_t B, const double *params, const
                           void *stream) {
   if (!h) return fail(nullptr, "cmpc_solve_batch_gain: null handle");
   if (!gain) return fail(h, "cmpc_solve_batch_gain: null gain (use cmpc_solve_batch_state for a solve without one)");
-  if (B > 0 && !h->gbuf) {                       // once per handle; hipMalloc synchronises the device
-    DeviceGuard guard(h->device);
-    if (!guard.ok) return fail(h, "cmpc_solve_batch_gain: cannot select the handle's device");
-    HIP_TRY(h, hipMalloc(&h->gbuf, (size_t)h->slabs * CMPC_NSTATE(h->spec.N, h->spec.nv) * sizeof(double)));
-  }
+  if (B > 0 && gbuf_ready(h, "cmpc_solve_batch_gain") != 0) return 1;
   return solve_batch(h, B, params, warm_XU, state_in, out_XU, state_out, status, iters, kkt_res, gain, nullptr, stream);
+}
+
+int cmpc_solve_batch_gain_consts(cmpc_handle *h, int32_t B, const double *params, const double *consts, const double *warm_XU,
+                                 const double *state_in, double *out_XU, double *state_out, int32_t *status, int32_t *iters,
+                                 double *kkt_res, double *gain, void *stream) {
+  if (!h) return fail(nullptr, "cmpc_solve_batch_gain_consts: null handle");
+  if (!gain) return fail(h, "cmpc_solve_batch_gain_consts: null gain (use cmpc_solve_batch_consts for a solve without one)");
+  if (!consts) return fail(h, "cmpc_solve_batch_gain_consts: null consts (use cmpc_solve_batch_gain for the handle's constants)");
+  if (B > 0 && gbuf_ready(h, "cmpc_solve_batch_gain_consts") != 0) return 1;
+  return solve_batch(h, B, params, warm_XU, state_in, out_XU, state_out, status, iters, kkt_res, gain, consts, stream);
+}
+
+int cmpc_gain_track(int32_t N, int32_t nv, int32_t B, const double *params, const double *XU, const double *gain,
+                    const double *x_meas, uint32_t columns, double *x1_out, double *u0_out, uint8_t *used, void *stream) {
+  if (N < 1 || N > CMPC_MAX_N || (nv != 4 && nv != 8) || B < 0) return fail(nullptr, "cmpc_gain_track: bad argument");
+  if (columns >> CMPC_NX) return fail(nullptr, "cmpc_gain_track: columns names a bit beyond the 20 words of x0");
+  if (B == 0) return 0;
+  if (!params || !XU || !gain || !x_meas || !x1_out || !u0_out || !used) return fail(nullptr, "cmpc_gain_track: null buffer");
+  const int nrec = CMPC_NREC(N), nsol = CMPC_NSOL(N, nv), u_at = CMPC_NX * (N + 1);
+  const int aligned = (((size_t)gain) & 15) == 0 ? 1 : 0;          // (a block is an even number of words: every pair is then aligned)
+  const int groups = (B + TRACK_WAVES - 1) / TRACK_WAVES, blocks = groups < 256 * 32 ? groups : 256 * 32;
+  const void *fn = (nv == 4) ? (const void *)cmpc_gain_track_kernel<4> : (const void *)cmpc_gain_track_kernel<8>;
+  void *args[] = {&B, (void *)&nrec, (void *)&nsol, (void *)&u_at, &params, &XU, &gain, &x_meas, &columns, (void *)&aligned, &x1_out, &u0_out, &used};
+  if (hipLaunchKernel(fn, dim3((unsigned)blocks), dim3(64 * TRACK_WAVES), args, 0, (hipStream_t)stream) != hipSuccess ||
+      hipGetLastError() != hipSuccess)
+    return fail(nullptr, "cmpc_gain_track: launch failed");
+  return 0;
 }
 
 int cmpc_last_kernel_ms(cmpc_handle *h, float *ms) {
@@ -876,7 +1008,7 @@ int cmpc_rollout_advance(const cmpc_tables *tb, int32_t N, int32_t nv, int32_t r
 
 const char *cmpc_last_kernel_name(cmpc_handle *h) { return h ? h->last_kernel : ""; }
 const char *cmpc_last_error(cmpc_handle *h) { return h ? h->err.c_str() : g_err.c_str(); }
-const char *cmpc_version(void) { return "cmpc_amd 0.5 (gfx950)"; }
+const char *cmpc_version(void) { return "cmpc_amd 0.6 (gfx950)"; }
 
 #ifdef CMPC_DEV_KNOBS
 /* developer build only: the first slab of the handle (the slab of workgroup 0), for dumps of a B = 1 launch */

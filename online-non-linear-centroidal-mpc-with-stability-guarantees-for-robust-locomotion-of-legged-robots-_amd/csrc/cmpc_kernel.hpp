@@ -2918,6 +2918,10 @@ template <int NV, int NW = 1, bool PIPE = false, bool GAIN = false, bool CONSTS 
         if (state_out) { GArr{state_out}[D::state_mu(N)] = 0.0; GArr{state_out}[D::state_mu(N) + 1] = 0.0; }
       }
     }
+    // (GAIN: no gain either -- the whole block NaN, written by the wave that writes every gain, as gain_tail does for a
+    // status 1 / 2.  The slot's saved iterate is not touched: a solve reads gbuf only after it has written it itself, so the
+    // next instance on this slot finds what it would have found.)
+    if constexpr (GAIN && CONSTS) { if (wv == 0) gain_step(false); }
     // (ends as solve() does: the lanes are together again before the caller's loop draws the next instance)
     if constexpr (PIPE) pair_sync(); else sync();
   }

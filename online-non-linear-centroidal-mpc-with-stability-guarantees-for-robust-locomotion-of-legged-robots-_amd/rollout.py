@@ -22,7 +22,9 @@ Everything after the solve is index arithmetic and copies in torch (device memor
 A fleet: with a ``workloads.SceneSet`` every instance walks the command of its own scene (``scene_id``): the records come
 from ``cmpc_build_records_scenes`` and step 3 is one launch, ``cmpc_rollout_advance``, indexed by (scene, tick); only the
 momentum lookup stays a torch gather.  With ``consts`` every instance is solved with its own 18 problem constants
-(``solve_with_consts``), with one scene or with a set.
+(``solve_with_consts``), with one scene or with a set.  With ``gains=True`` every tick also returns the first-stage gains
+(``solve_with_gain``, with the instances' own constants when there are any; the trajectory is the same bit for bit) and
+``track`` applies them to a measured state between two solves.
 """
 import numpy as np
 import torch
@@ -48,10 +50,12 @@ def _checked_consts(consts, spec, B):
 
 class BatchedRollout:
     def __init__(self, scene, spec, B, device="cuda:0", mass=None, mu=0.5, update_contact=True,
-                 hw_measured=None, hw_offset=None, rate=1, scene_id=None, consts=None):
+                 hw_measured=None, hw_offset=None, rate=1, scene_id=None, consts=None, gains=False):
         """scene: a ``workloads.Scene`` (one walk for the batch) or a ``workloads.SceneSet`` with ``scene_id`` (B,) naming
         every instance's walk (optional for a set of one).  hw_measured: one recording (ticks, 3), or with a set one per
-        scene.  consts (B, 18): per-instance problem constants, every row with the spec's delta."""
+        scene.  consts (B, 18): per-instance problem constants, every row with the spec's delta.
+        gains: every tick solves through ``solve_with_gain`` and keeps ``last_gain`` (B, 20 + nu, 20) next to
+        ``last_records`` and ``last_XU`` (``track``); it is one buffer, overwritten by the next tick."""
         consts = None if consts is None else _checked_consts(consts, spec, B)
         self._set = scene if isinstance(scene, SceneSet) else None
         if self._set is None and scene_id is not None:
@@ -70,6 +74,7 @@ class BatchedRollout:
         self.builder = DeviceRecordBuilder(scene, device=self.device)
         dev, f64 = self.device, torch.float64
         self.consts = None if consts is None else torch.from_numpy(consts).to(dev)
+        self.gains, self.last_gain = bool(gains), None
         self.state = torch.zeros((B, 16), dtype=f64, device=dev)
         self.state[:, 14] = scene.params['mass'] if mass is None else torch.as_tensor(mass, dtype=f64, device=dev)
         self.state[:, 15] = torch.as_tensor(mu, dtype=f64, device=dev)
@@ -197,9 +202,21 @@ class BatchedRollout:
             self.plan_pos = torch.from_numpy(self.scene.plan_pos).to(dev).repeat(self.B, 1, 1).contiguous()
 
     def _solve_tick(self, rec, s_in, s_out):
+        if self.gains:
+            # (one gain buffer for the rollout: every tick writes all of it)
+            *res, self.last_gain = self.solver.solve_with_gain(rec, warm=self.warm, state=s_in, state_out=s_out, gain=self.last_gain,
+                                                               consts=self.consts)
+            return tuple(res)
         if self.consts is not None:
             return self.solver.solve_with_consts(rec, self.consts, warm=self.warm, state=s_in, state_out=s_out)
         return self.solver.solve(rec, warm=self.warm, state=s_in, state_out=s_out)
+
+    def track(self, x_meas, columns=0xFFF):
+        """The last tick's gain applied to a measured state x_meas (B, 20), in the layout of x0: (x1, u0, used) of
+        ``BatchedCentroidalMPC.track`` on ``last_records``, ``last_XU`` and ``last_gain``.  Needs ``gains=True`` and a tick."""
+        if self.last_gain is None:
+            raise RuntimeError("track needs a rollout built with gains=True that has made a step")
+        return self.solver.track(self.last_records, self.last_XU, self.last_gain, x_meas, columns=columns)
 
     def _step_set(self, push_dv):
         """``step`` of a fleet: records by (scene, tick), the solve, then the back half in one launch."""

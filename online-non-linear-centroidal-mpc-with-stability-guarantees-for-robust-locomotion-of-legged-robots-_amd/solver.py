@@ -120,7 +120,10 @@ class BatchedCentroidalMPC:
                 state.data_ptr() if state is not None else None, out.data_ptr(),
                 state_out.data_ptr() if state_out is not None else None,
                 status.data_ptr(), iters.data_ptr(), kkt.data_ptr())
-        if consts is not None:
+        if consts is not None and gain is not None:
+            rc = self._lib.cmpc_solve_batch_gain_consts(*args[:3], consts.data_ptr(), *args[3:], gain.data_ptr(),
+                                                        ctypes.c_void_p(stream))
+        elif consts is not None:
             rc = self._lib.cmpc_solve_batch_consts(*args[:3], consts.data_ptr(), *args[3:], ctypes.c_void_p(stream))
         elif gain is None:
             rc = self._lib.cmpc_solve_batch_state(*args, ctypes.c_void_p(stream))
@@ -130,8 +133,10 @@ class BatchedCentroidalMPC:
             raise RuntimeError("cmpc_solve_batch failed: " + self._lib.cmpc_last_error(self._h).decode())
         return out, status, iters, kkt
 
-    def solve_with_gain(self, records, warm=None, out=None, state=None, state_out=None, gain=None):
+    def solve_with_gain(self, records, warm=None, out=None, state=None, state_out=None, gain=None, consts=None):
         """``solve`` plus the first-stage feedback gain: (XU, status, iters, kkt, G), G (B, 20 + nu, 20) on the GPU.
+        With ``consts`` (B, 18), as ``solve_with_consts`` takes them, every instance is solved -- and its gain taken -- with
+        its own row (``cmpc_solve_batch_gain_consts``); an instance whose row is refused has a gain of NaN.
 
         G[b] = d(x_1, u_0)/dx0 of instance b: rows X[:,1] (20) then U[:,0] (nu), one column per component of
         x0 = records[b, 0:20]; every other record entry and the proximal centre ``warm`` stay fixed.  XU, status,
@@ -150,8 +155,49 @@ class BatchedCentroidalMPC:
         elif not (gain.is_cuda and gain.dtype == torch.float64 and gain.is_contiguous() and tuple(gain.shape) == shape
                   and gain.device == self.device):
             raise ValueError(f"gain must be a contiguous fp64 CUDA tensor of shape {shape}")
-        out, status, iters, kkt = self._solve(records, warm, out, state, state_out, gain)
+        if consts is not None and not isinstance(consts, torch.Tensor):
+            raise ValueError(f"consts must be a contiguous fp64 CUDA tensor of shape (B, {NCONST})")
+        out, status, iters, kkt = self._solve(records, warm, out, state, state_out, gain, consts)
         return out, status, iters, kkt, gain
+
+    def track(self, records, XU, gain, x_meas, columns=0xFFF, x1_out=None, u0_out=None):
+        """The gain applied between two solves, one launch that reads the gains once (``cmpc_gain_track``, include/cmpc.h):
+        (x1, u0, used) with x1 (B, 20) = X[:,1] + G[:20] dx, u0 (B, nu) = U[:,0] + G[20:] dx and used (B,) bool, where
+        dx = x_meas - x0 on the columns whose bit is set in ``columns`` (default: the centroidal state; INTEGRATION.md on why
+        the foot columns are usually left out) and 0 elsewhere, x0 = records[:, 0:20].  An instance holds -- X[:,1], U[:,0]
+        as they are, used False -- when any word of its gain, or a chosen word of x_meas or x0, is not finite.
+        Asynchronous on torch's current stream, no allocation beyond the outputs."""
+        sp, dev, f64 = self.spec, self.device, torch.float64
+
+        def ok(x, dtype, shape):
+            return (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == dtype and x.is_contiguous()
+                    and tuple(x.shape) == shape and x.device == dev)
+        if not (isinstance(records, torch.Tensor) and records.dim() == 2):
+            raise ValueError(f"records must be a contiguous fp64 CUDA tensor of shape (B, {sp.nrec})")
+        B = records.shape[0]
+        if not (ok(records, f64, (B, sp.nrec)) and ok(XU, f64, (B, sp.nsol)) and ok(gain, f64, (B, NX + sp.nu, NX))
+                and ok(x_meas, f64, (B, NX))):
+            raise ValueError(f"track: records (B, {sp.nrec}), XU (B, {sp.nsol}), gain (B, {NX + sp.nu}, {NX}) and x_meas "
+                             f"(B, {NX}) must be contiguous fp64 tensors on {dev}")
+        columns = int(columns)
+        if columns < 0 or columns >> NX:
+            raise ValueError(f"columns must name bits 0..{NX - 1} only")
+        if x1_out is None:
+            x1_out = torch.empty((B, NX), dtype=f64, device=dev)
+        if u0_out is None:
+            u0_out = torch.empty((B, sp.nu), dtype=f64, device=dev)
+        if not (ok(x1_out, f64, (B, NX)) and ok(u0_out, f64, (B, sp.nu))):
+            raise ValueError(f"track: x1_out (B, {NX}) and u0_out (B, {sp.nu}) must be contiguous fp64 tensors on {dev}")
+        used = torch.empty(B, dtype=torch.bool, device=dev)
+        if B == 0:
+            return x1_out, u0_out, used
+        with torch.cuda.device(dev):                           # (the entry point takes no handle: the current device's)
+            stream = torch.cuda.current_stream(dev).cuda_stream
+            rc = self._lib.cmpc_gain_track(sp.N, sp.nv, B, records.data_ptr(), XU.data_ptr(), gain.data_ptr(), x_meas.data_ptr(),
+                                           columns, x1_out.data_ptr(), u0_out.data_ptr(), used.data_ptr(), ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError("cmpc_gain_track failed: " + self._lib.cmpc_last_error(None).decode())
+        return x1_out, u0_out, used
 
     def new_state(self, B):
         """An empty solver state for B instances (barrier word 0 = "no state": the first tick starts cold)."""
