@@ -18,9 +18,12 @@ CSRC = os.path.join(PKG, "csrc")
 # the solver's device source, which the host emulation and the device unit harness compile as well
 KERNEL_DEPS = [os.path.join(CSRC, "cmpc_kernel.hpp"), os.path.join(CSRC, "cmpc_lds_asm.hpp"), os.path.join(CSRC, "cmpc_wave.hpp"),
                os.path.join(ROOT, "include", "cmpc.h")]
-# everything the HIP library (and each of its diagnostic variants) is built from; the first two are the translation units:
-# the solver and the batched whole-body QP (include/cmpc_wbc.h), same library
-DEVICE_DEPS = [os.path.join(CSRC, "cmpc_hip.hip"), os.path.join(CSRC, "wbc_qp.hip")] + KERNEL_DEPS + [
+# everything the HIP library (and each of its diagnostic variants) is built from; DEVICE_UNITS are the translation units:
+# the solver, the batched whole-body QP (include/cmpc_wbc.h) and the batched rigid-body model (include/cmpc_rbd.h), same library
+# the device source of the batched rigid-body model (include/cmpc_rbd.h), which tests/emu/rbd_emu.cpp compiles as well
+RBD_DEPS = [os.path.join(CSRC, "rbd_kernel.hpp"), os.path.join(ROOT, "include", "cmpc_rbd.h")]
+DEVICE_UNITS = [os.path.join(CSRC, "cmpc_hip.hip"), os.path.join(CSRC, "wbc_qp.hip"), os.path.join(CSRC, "rbd.hip")]
+DEVICE_DEPS = DEVICE_UNITS + KERNEL_DEPS + RBD_DEPS + [
     os.path.join(CSRC, "cmpc_order_fit.h"), os.path.join(ROOT, "include", "cmpc_wbc.h")]
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 
@@ -29,7 +32,7 @@ def _hipcc_lib(out, defines=(), force=False, verbose=False):
     if force or _newer(out, DEVICE_DEPS):
         subprocess.check_call(["hipcc"] + (["-Rpass-analysis=kernel-resource-usage"] if verbose else [])
                               + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared"]
-                              + ["-D" + d for d in defines] + ["-o", out] + DEVICE_DEPS[:2])
+                              + ["-D" + d for d in defines] + ["-o", out] + DEVICE_UNITS)
     return out
 
 
@@ -118,6 +121,16 @@ def build_emu_step(force=False, fused=True):
                     [] if fused else ["CMPC_SEPARATE_STEP"], force)
 
 
+def build_emu_rbd(force=False):
+    """Host emulation of the batched rigid-body model (tests/emu/rbd_emu.cpp): test harness only."""
+    src, out = os.path.join(EMU_DIR, "rbd_emu.cpp"), os.path.join(EMU_DIR, "librbd_emu.so")
+    if force or _newer(out, [src] + RBD_DEPS):
+        # (-ffp-contract=off: the kernel source forms every product and sum as written, in both of its builds)
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-fPIC", "-shared", "-pthread",
+                               "-o", out, src])
+    return out
+
+
 def build_device_unit(force=False):
     """GPU-tier unit harness for the device-only primitives (tests/gpu_unit): never loaded by the package."""
     src = os.path.join(ROOT, "tests", "gpu_unit", "cmpc_device_unit.hip")
@@ -156,5 +169,6 @@ if __name__ == "__main__":
     print(build_emu_reuse(force, reuse=False))
     print(build_emu_step(force))
     print(build_emu_step(force, fused=False))
+    print(build_emu_rbd(force))
     print(build_device_unit(force))
     print(build_tools(force))

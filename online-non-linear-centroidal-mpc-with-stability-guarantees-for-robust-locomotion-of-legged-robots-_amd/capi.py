@@ -24,6 +24,8 @@ SYMBOLS = ("cmpc_default_spec", "cmpc_create", "cmpc_destroy", "cmpc_workspace_b
            "cmpc_scenes_create", "cmpc_build_records_scenes", "cmpc_scenes_set_schedule", "cmpc_rollout_advance")
 #: every symbol include/cmpc_wbc.h declares (batched whole-body QP, same library)
 WBC_SYMBOLS = ("cmpc_wbc_qp_solve_batch", "cmpc_wbc_qp_solve_tasks", "cmpc_wbc_default_gains", "cmpc_wbc_last_error")
+#: every symbol include/cmpc_rbd.h declares (batched rigid-body model, same library)
+RBD_SYMBOLS = ("cmpc_rbd_model_create", "cmpc_rbd_model_destroy", "cmpc_rbd_eval", "cmpc_rbd_last_error")
 
 
 class WbcGains(ctypes.Structure):
@@ -101,6 +103,14 @@ def load():
     lib.cmpc_wbc_default_gains.restype = None
     lib.cmpc_wbc_last_error.argtypes = []
     lib.cmpc_wbc_last_error.restype = ctypes.c_char_p
+    lib.cmpc_rbd_model_create.argtypes = [ctypes.c_int] + [vp] * 10 + [ctypes.POINTER(vp)]
+    lib.cmpc_rbd_model_create.restype = ctypes.c_int
+    lib.cmpc_rbd_model_destroy.argtypes = [vp]
+    lib.cmpc_rbd_model_destroy.restype = ctypes.c_int
+    lib.cmpc_rbd_eval.argtypes = [vp, i32, vp, vp, f64] + [vp] * 8
+    lib.cmpc_rbd_eval.restype = ctypes.c_int
+    lib.cmpc_rbd_last_error.argtypes = []
+    lib.cmpc_rbd_last_error.restype = ctypes.c_char_p
     lib.cmpc_version.argtypes = []
     lib.cmpc_version.restype = ctypes.c_char_p
     _lib = lib

@@ -1,0 +1,332 @@
+"""Batched rigid-body model (include/cmpc_rbd.h, csrc/rbd_kernel.hpp): what the reference takes from DART every tick --
+the task Jacobians, their bias accelerations, the mass matrix and the Coriolis + gravity vector of
+code/inverse_dynamics.py:46-65, :112, :116, and the measured ``current`` of code/simulation.py:303-388 -- for B robots in
+one HIP launch, in the layouts ``BatchedInverseDynamicsQP.solve_tasks`` and ``BatchedCentroidalMPC.track`` consume.
+
+``RobotModel`` is the host side (numpy and the standard library): a kinematic tree parsed from a URDF, fixed joints merged,
+validated so that no table can index outside the kernel's arrays.  ``BatchedRobot`` is the device side; there is no CPU
+fallback.
+
+Coordinates (this build's own: parity with DART's is not pinned by any test): q[0:3] is the rotation
+vector of the base, R_b = Exp(q[0:3]) (world <- base), q[3:6] the base origin in the world, q[6+k] the joint angles in URDF
+file order; v[0:3] and v[3:6] are the base angular and base-origin linear velocity in the BASE frame (the body twist),
+v[6+k] the joint rates.  M, h are those of M vdot + h = S' tau + Jc' f with vdot the plain time derivative of v.
+"""
+import collections
+import ctypes
+import xml.etree.ElementTree as ET
+
+import numpy as np
+
+BODIES, DOFS, BASE, FRAMES, ROWS = 25, 30, 6, 4, 21
+FRAME_ORDER = ('lfoot', 'rfoot', 'torso', 'base')
+DEFAULT_FRAMES = {'lfoot': 'l_sole', 'rfoot': 'r_sole', 'torso': 'torso', 'base': 'body'}
+BASE_DOF_NAMES = ('base_rot_x', 'base_rot_y', 'base_rot_z', 'base_pos_x', 'base_pos_y', 'base_pos_z')
+#: code/simulation.py:88-91
+HRP4_REDUNDANT_DOFS = ("NECK_Y", "NECK_P", "R_SHOULDER_P", "R_SHOULDER_R", "R_SHOULDER_Y", "R_ELBOW_P",
+                       "L_SHOULDER_P", "L_SHOULDER_R", "L_SHOULDER_Y", "L_ELBOW_P")
+#: code/simulation.py:63-67, degrees
+HRP4_INITIAL_DEG = {'CHEST_P': 0., 'CHEST_Y': 0., 'NECK_P': 0., 'NECK_Y': 0.,
+                    'R_HIP_Y': 0., 'R_HIP_R': -3., 'R_HIP_P': -25., 'R_KNEE_P': 50., 'R_ANKLE_P': -25., 'R_ANKLE_R': 3.,
+                    'L_HIP_Y': 0., 'L_HIP_R': 3., 'L_HIP_P': -25., 'L_KNEE_P': 50., 'L_ANKLE_P': -25., 'L_ANKLE_R': -3.,
+                    'R_SHOULDER_P': 4., 'R_SHOULDER_R': -8., 'R_SHOULDER_Y': 0., 'R_ELBOW_P': -25.,
+                    'L_SHOULDER_P': 4., 'L_SHOULDER_R': 8., 'L_SHOULDER_Y': 0., 'L_ELBOW_P': -25.}
+
+Evaluation = collections.namedtuple("Evaluation", "J jdqd M h pose vel centroid")
+
+
+def rpy_matrix(rpy):
+    """URDF's fixed-axis roll, pitch, yaw: R = Rz(yaw) Ry(pitch) Rx(roll)."""
+    r, p, y = (float(a) for a in rpy)
+    cr, sr, cp, sp, cy, sy = np.cos(r), np.sin(r), np.cos(p), np.sin(p), np.cos(y), np.sin(y)
+    return np.array([[cy * cp, cy * sp * sr - sy * cr, cy * sp * cr + sy * sr],
+                     [sy * cp, sy * sp * sr + cy * cr, sy * sp * cr - cy * sr],
+                     [-sp, cp * sr, cp * cr]])
+
+
+def axis_rotation(a, q):
+    """Rotation by q about the unit axis a."""
+    K = np.array([[0., -a[2], a[1]], [a[2], 0., -a[0]], [-a[1], a[0], 0.]])
+    return np.eye(3) + np.sin(q) * K + (1. - np.cos(q)) * (K @ K)
+
+
+def exp_so3(w):
+    w = np.asarray(w, dtype=np.float64)
+    t = np.linalg.norm(w)
+    return np.eye(3) if t == 0. else axis_rotation(w / t, t)
+
+
+def _vec(text, default):
+    return np.array([float(x) for x in (text.split() if text else default.split())])
+
+
+def _origin(el):
+    o = None if el is None else el.find('origin')
+    xyz = _vec(None if o is None else o.get('xyz'), '0 0 0')
+    rpy = _vec(None if o is None else o.get('rpy'), '0 0 0')
+    if xyz.shape != (3,) or rpy.shape != (3,):
+        raise ValueError("an <origin> needs three numbers in xyz and in rpy")
+    return rpy_matrix(rpy), xyz
+
+
+def _orthonormal(R):
+    """R'R = I to 1e-9 for every matrix of the stack (the native validation's rule)."""
+    return bool(np.all(np.abs(np.swapaxes(R, -1, -2) @ R - np.eye(3)) < 1e-9))
+
+
+def _sym6(I):
+    return np.array([I[0, 0], I[0, 1], I[0, 2], I[1, 1], I[1, 2], I[2, 2]])
+
+
+class RobotModel:
+    """The validated tables of ``cmpc_rbd_model_create``: body 0 is the floating base, body i (1..24) hangs on
+    ``parent[i] < i`` by a revolute joint and is moved by dof 5 + i.  ``joint_names``: the 24 joints in dof order."""
+
+    def __init__(self, parent, joint_R, joint_p, axis, mass, com, inertia, frame_body, frame_R, frame_p, joint_names=None):
+        f64 = np.float64
+        self.parent = np.ascontiguousarray(parent, dtype=np.int32)
+        self.joint_R = np.ascontiguousarray(joint_R, dtype=f64)
+        self.joint_p = np.ascontiguousarray(joint_p, dtype=f64)
+        self.axis = np.array(axis, dtype=f64, order='C')
+        self.mass = np.ascontiguousarray(mass, dtype=f64)
+        self.com = np.ascontiguousarray(com, dtype=f64)
+        self.inertia = np.ascontiguousarray(inertia, dtype=f64)
+        self.frame_body = np.ascontiguousarray(frame_body, dtype=np.int32)
+        self.frame_R = np.ascontiguousarray(frame_R, dtype=f64)
+        self.frame_p = np.ascontiguousarray(frame_p, dtype=f64)
+        for name, a, shape in (("parent", self.parent, (BODIES,)), ("joint_R", self.joint_R, (BODIES, 3, 3)),
+                               ("joint_p", self.joint_p, (BODIES, 3)), ("axis", self.axis, (BODIES, 3)),
+                               ("mass", self.mass, (BODIES,)), ("com", self.com, (BODIES, 3)),
+                               ("inertia", self.inertia, (BODIES, 6)), ("frame_body", self.frame_body, (FRAMES,)),
+                               ("frame_R", self.frame_R, (FRAMES, 3, 3)), ("frame_p", self.frame_p, (FRAMES, 3))):
+            if a.shape != shape:
+                raise ValueError(f"{name} must have shape {shape}: this build serves trees with exactly {BODIES - 1} "
+                                 f"one-dof joints ({DOFS} dofs with the floating base), got {a.shape}")
+        if self.parent[0] != -1 or any(not (0 <= self.parent[i] < i) for i in range(1, BODIES)):
+            raise ValueError("parents must be ordered: parent[0] = -1 and 0 <= parent[i] < i")
+        n = np.linalg.norm(self.axis[1:], axis=1)
+        if not (np.all(np.isfinite(self.axis[1:])) and np.all(n > 1e-12)):
+            raise ValueError("joint axes must be finite and non-zero")
+        self.axis[1:] /= n[:, None]
+        self.axis[0] = (0., 0., 1.)
+        if not (np.all(np.isfinite(self.joint_R)) and np.all(np.isfinite(self.joint_p))):
+            raise ValueError("joint placements must be finite")
+        if not _orthonormal(self.joint_R[1:]):
+            raise ValueError("joint rotations must be orthonormal")
+        if not (np.all(np.isfinite(self.mass)) and np.all(self.mass >= 0.) and self.mass.sum() > 0.):
+            raise ValueError("masses must be finite and >= 0, with a total > 0")
+        if not np.all(np.isfinite(self.inertia)):
+            raise ValueError("inertias must be finite")
+        if not np.all(np.isfinite(self.com)):
+            raise ValueError("centres of mass must be finite")
+        if not (np.all((0 <= self.frame_body) & (self.frame_body < BODIES)) and np.all(np.isfinite(self.frame_R))
+                and np.all(np.isfinite(self.frame_p))):
+            raise ValueError("task frames must sit on a body of the tree, with finite placements")
+        if not _orthonormal(self.frame_R):
+            raise ValueError("task frame rotations must be orthonormal")
+        self.joint_names = tuple(joint_names) if joint_names is not None else tuple(f"joint_{i}" for i in range(BODIES - 1))
+        if len(self.joint_names) != BODIES - 1:
+            raise ValueError(f"{BODIES - 1} joint names expected")
+        self.dof_names = BASE_DOF_NAMES + self.joint_names
+        self.total_mass = float(self.mass.sum())
+
+    # ---- parsing ---------------------------------------------------------------------------------------------------------
+    @classmethod
+    def from_urdf(cls, path, frames=None):
+        """Parse a URDF: ``revolute`` / ``continuous`` joints give one dof each, in file order; ``fixed`` joints are merged
+        into the parent body (mass, centre of mass and inertia by the parallel-axis rule, ``<inertial><origin rpy>``
+        honoured; a task frame on a merged link becomes a fixed offset on the body that absorbed it); any other joint type
+        is refused.  ``frames``: link names of the task frames lfoot, rfoot, torso, base."""
+        frames = dict(DEFAULT_FRAMES, **(frames or {}))
+        root = ET.parse(path).getroot()
+        links = {}
+        for el in root.findall('link'):
+            ine = el.find('inertial')
+            m, c, I = 0., np.zeros(3), np.zeros((3, 3))
+            if ine is not None:
+                R, c = _origin(ine)
+                mel, iel = ine.find('mass'), ine.find('inertia')
+                m = float(mel.get('value')) if mel is not None else 0.
+                if iel is not None:
+                    g = lambda k: float(iel.get(k, '0'))
+                    I = np.array([[g('ixx'), g('ixy'), g('ixz')], [g('ixy'), g('iyy'), g('iyz')], [g('ixz'), g('iyz'), g('izz')]])
+                    I = R @ I @ R.T
+            links[el.get('name')] = (m, c, I)
+        joints = []
+        for el in root.findall('joint'):
+            kind = el.get('type')
+            if kind not in ('revolute', 'continuous', 'fixed'):
+                raise ValueError(f"joint {el.get('name')!r}: type {kind!r} is not supported (revolute, continuous, fixed)")
+            R, p = _origin(el)
+            ax = el.find('axis')
+            joints.append(dict(name=el.get('name'), kind=kind, R=R, p=p, parent=el.find('parent').get('link'),
+                               child=el.find('child').get('link'), axis=_vec(None if ax is None else ax.get('xyz'), '1 0 0')))
+        children = {j['child'] for j in joints}
+        roots = [n for n in links if n not in children]
+        if len(roots) != 1:
+            raise ValueError(f"the URDF must have exactly one root link, found {roots}")
+        moving = [j for j in joints if j['kind'] != 'fixed']
+        if len(moving) != BODIES - 1:
+            raise ValueError(f"this build serves trees with exactly {BODIES - 1} one-dof joints ({DOFS} dofs with the "
+                             f"floating base): the URDF has {len(moving)}")
+        # link -> (body, R, p): the link's frame in the body that carries it
+        place = {roots[0]: (0, np.eye(3), np.zeros(3))}
+        parent = np.full(BODIES, -1, dtype=np.int32)
+        joint_R, joint_p = np.tile(np.eye(3), (BODIES, 1, 1)), np.zeros((BODIES, 3))
+        axis = np.tile(np.array([0., 0., 1.]), (BODIES, 1))
+        index = {j['name']: 1 + k for k, j in enumerate(moving)}
+        pending = list(joints)
+        while pending:
+            ready = [j for j in pending if j['parent'] in place]
+            if not ready:
+                raise ValueError("the URDF's joints do not form a tree on its root link")
+            for j in ready:
+                if j['child'] in place:
+                    raise ValueError(f"link {j['child']!r} has two parents")
+                b, Rb, pb = place[j['parent']]
+                R, p = Rb @ j['R'], pb + Rb @ j['p']
+                if j['kind'] == 'fixed':
+                    place[j['child']] = (b, R, p)
+                else:
+                    i = index[j['name']]
+                    parent[i], joint_R[i], joint_p[i], axis[i] = b, R, p, j['axis']
+                    place[j['child']] = (i, np.eye(3), np.zeros(3))
+            pending = [j for j in pending if j not in ready]
+        mass, com, inertia = np.zeros(BODIES), np.zeros((BODIES, 3)), np.zeros((BODIES, 6))
+        for b in range(BODIES):
+            parts = [(links[n][0], p + R @ links[n][1], R @ links[n][2] @ R.T) for n, (bb, R, p) in place.items() if bb == b]
+            m = sum(x[0] for x in parts)
+            c = sum(x[0] * x[1] for x in parts) / m if m > 0. else np.zeros(3)
+            I = np.zeros((3, 3))
+            for mk, ck, Ik in parts:                                          # parallel axes, to the body's centre of mass
+                d = ck - c
+                I = I + Ik + mk * (d @ d * np.eye(3) - np.outer(d, d))
+            mass[b], com[b], inertia[b] = m, c, _sym6(I)
+        fb, fR, fp = np.zeros(FRAMES, dtype=np.int32), np.zeros((FRAMES, 3, 3)), np.zeros((FRAMES, 3))
+        for k, name in enumerate(FRAME_ORDER):
+            if frames[name] not in place:
+                raise ValueError(f"task frame {name!r}: the URDF has no link {frames[name]!r}")
+            fb[k], fR[k], fp[k] = place[frames[name]]
+        return cls(parent, joint_R, joint_p, axis, mass, com, inertia, fb, fR, fp, joint_names=[j['name'] for j in moving])
+
+    # ---- host helpers ----------------------------------------------------------------------------------------------------
+    def tables(self):
+        """The arrays of ``cmpc_rbd_model_create``, in its argument order."""
+        return (self.parent, self.joint_R, self.joint_p, self.axis, self.mass, self.com, self.inertia, self.frame_body,
+                self.frame_R, self.frame_p)
+
+    def joint_selection(self, names):
+        """The diagonal (30,) of ``joint_selection`` (code/inverse_dynamics.py:24-28): 1 at the dofs named."""
+        sel = np.zeros(DOFS)
+        for n in names:
+            sel[self.dof_names.index(n)] = 1.
+        return sel
+
+    def configuration(self, angles, degrees=False):
+        """q (30,) with the base at the origin and the joints named in ``angles`` set (the others 0)."""
+        q = np.zeros(DOFS)
+        for n, a in angles.items():
+            q[self.dof_names.index(n)] = np.deg2rad(a) if degrees else a
+        return q
+
+    def body_poses(self, q):
+        """World rotations (25,3,3) and origins (25,3) of the bodies at q (30,): plain forward kinematics on the host."""
+        q = np.asarray(q, dtype=np.float64)
+        R, p = np.zeros((BODIES, 3, 3)), np.zeros((BODIES, 3))
+        R[0], p[0] = exp_so3(q[0:3]), q[3:6]
+        for i in range(1, BODIES):
+            k = self.parent[i]
+            R[i] = R[k] @ self.joint_R[i] @ axis_rotation(self.axis[i], q[5 + i])
+            p[i] = p[k] + R[k] @ self.joint_p[i]
+        return R, p
+
+    def frame_poses(self, q):
+        """name -> (R (3,3), p (3,)) of the task frames at q, and 'com' -> p."""
+        R, p = self.body_poses(q)
+        out = {n: (R[b] @ self.frame_R[k], p[b] + R[b] @ self.frame_p[k]) for k, (n, b) in enumerate(zip(FRAME_ORDER, self.frame_body))}
+        out['com'] = sum(self.mass[i] * (p[i] + R[i] @ self.com[i]) for i in range(BODIES)) / self.total_mass
+        return out
+
+    def place_on_ground(self, q):
+        """q with the base origin moved so that the midpoint of the soles is the world origin (code/simulation.py:73-77)."""
+        q = np.array(q, dtype=np.float64)
+        f = self.frame_poses(q)
+        q[3:6] -= (f['lfoot'][1] + f['rfoot'][1]) / 2.
+        return q
+
+
+class BatchedRobot:
+    """``RobotModel`` on the GPU: ``evaluate(q, v)`` is one launch of csrc/rbd_kernel.hpp for the whole batch."""
+
+    def __init__(self, model, device="cuda:0", g=9.81):
+        import torch
+        from . import capi
+        if not torch.cuda.is_available():
+            raise RuntimeError("BatchedRobot needs a ROCm GPU: there is no CPU fallback")
+        self.model, self.g = model, float(g)
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self._lib = capi.load()
+        self._handle = ctypes.c_void_p()
+        self._tables = model.tables()                    # (kept: the pointers are read during the call only, but cheap)
+        rc = self._lib.cmpc_rbd_model_create(self.device.index, *(a.ctypes.data for a in self._tables), ctypes.byref(self._handle))
+        if rc != 0:
+            raise ValueError(self._lib.cmpc_rbd_last_error().decode())
+        self.joint_sel = None
+
+    def __del__(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            self._lib.cmpc_rbd_model_destroy(h)
+
+    def evaluate(self, q, v, outputs=Evaluation._fields):
+        """q, v (B,30) contiguous fp64 on this GPU -> ``Evaluation(J (B,21,30), jdqd (B,21), M (B,30,30), h (B,30), pose
+        (B,21), vel (B,21), centroid (B,9))`` on the current stream.  ``outputs``: the fields wanted; the others are None
+        (the kernel skips them)."""
+        import torch
+        B = q.shape[0]
+        for name, t in (("q", q), ("v", v)):
+            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
+                    and tuple(t.shape) == (B, DOFS) and t.device == self.device):
+                raise ValueError(f"{name} must be a contiguous fp64 tensor of shape ({B}, {DOFS}) on {self.device}")
+        shapes = dict(J=(B, ROWS, DOFS), jdqd=(B, ROWS), M=(B, DOFS, DOFS), h=(B, DOFS), pose=(B, ROWS), vel=(B, ROWS),
+                      centroid=(B, 9))
+        unknown = set(outputs) - set(shapes)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        out = {k: (torch.empty(shapes[k], dtype=torch.float64, device=self.device) if k in outputs else None) for k in Evaluation._fields}
+        if B > 0:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self._lib.cmpc_rbd_eval(self._handle, B, q.data_ptr(), v.data_ptr(), self.g,
+                                         *(None if out[k] is None else out[k].data_ptr() for k in Evaluation._fields),
+                                         ctypes.c_void_p(stream))
+            if rc != 0:
+                raise RuntimeError(self._lib.cmpc_rbd_last_error().decode())
+        return Evaluation(**out)
+
+    def task_model(self, q, v, redundant_dofs=HRP4_REDUNDANT_DOFS):
+        """A callable for ``BatchedRollout.attach_whole_body_tasks(qp, model)``.  q, v: (B,30) device tensors the caller may
+        update in place between ticks.  Per tick it evaluates the kernel and returns the ``solve_tasks`` inputs with
+        Jdot = None and -jdqd folded into the feed-forward; the CoM rows follow the MPC's ``desired`` (com_acc,
+        com_pos - pose, com_vel - vel), every other error and feed-forward is zero (the robot holds its pose), and
+        joint_selection is that of ``redundant_dofs``.  ``last_evaluation`` keeps the tick's kernel outputs."""
+        import torch
+        sel = torch.from_numpy(self.model.joint_selection(redundant_dofs)).to(self.device)
+        nacc = ROWS + DOFS
+
+        def model(rollout, desired):
+            ev = self.evaluate(q, v)
+            model.last_evaluation = ev
+            B = q.shape[0]
+            ff = torch.zeros((B, nacc), dtype=torch.float64, device=self.device)
+            pe = torch.zeros((B, nacc), dtype=torch.float64, device=self.device)
+            ve = torch.zeros((B, nacc), dtype=torch.float64, device=self.device)
+            ff[:, :ROWS] = -ev.jdqd
+            ff[:, 12:15] += desired["com_acc"]
+            pe[:, 12:15] = desired["com_pos"] - ev.pose[:, 12:15]
+            ve[:, 12:15] = desired["com_vel"] - ev.vel[:, 12:15]
+            return ev.J, None, ff, pe, ve, None, ev.M, ev.h, sel
+
+        model.last_evaluation = None
+        return model
