@@ -1,0 +1,72 @@
+/*
+ * cmpc_walk.h -- C ABI of the walking loop around the batched rigid-body model (libcmpc_amd.so): the whole-body task
+ * references of B robots from each robot's own adapted plan (code/simulation.py:227-231, :269-271 and
+ * code/inverse_dynamics.py:68-89 of the reference) and the step that advances (q, v) by the whole-body QP's acceleration,
+ * one launch each.  Coordinates and task rows are those of include/cmpc_rbd.h and include/cmpc_wbc.h.
+ *
+ * cmpc_walk_gait_create: HOST tables of S walks, row-major, padded per scene (padding is never read):
+ *   T          [S]                  ticks of each scene, 1 <= T[s] <= T_max
+ *   step_idx   [S][T_max]           step index at every tick, 0 <= step_idx < n_steps[s]
+ *   n_steps    [S]                  plan entries, 1 <= n_steps[s] <= n_steps_max
+ *   step_start [S][n_steps_max]     first tick of each step; step_start[step_idx[t]] <= t
+ *   ss_dur     [S][n_steps_max]     single-support ticks, > 0 (entry 0, the initial double support: >= 0)
+ *   support_l  [S][n_steps_max]     uint8, 1 where the support foot is the left one
+ *   ang        [S][n_steps_max][3]  orientation of each plan entry (finite)
+ *   init_feet  [S][12]              initial lfoot, rfoot poses as [ang, pos] (finite)
+ *   step_height, delta              swing apex; the world time step, > 0
+ * Everything is validated on the host, so that no entry can index outside an array.
+ *
+ * cmpc_walk_task_refs: DEVICE pointers, instance-major.
+ *   t [B] int32, scene_id [B] int32 (NULL = scene 0)
+ *   plan_pos [B][n_steps_max][3]    the plan cmpc_rollout_advance writes
+ *   pose, vel, jdqd [B][21]         of cmpc_rbd_eval            com_des [B][9]  desired CoM position, velocity, acceleration
+ *   q, v [B][30]                    q_ref [30]  the posture the joint task holds (NULL = zeros); its velocity is 0
+ *   ff, pos_err, vel_err [B][51]    the inputs of cmpc_wbc_qp_solve_tasks with Jdot = NULL (-jdqd folded into ff)
+ *   feet_des [B][36]                lfoot [ang, pos] 6, velocity 6, acceleration 6; then rfoot
+ * Any output may be NULL (skipped).  The desired feet are the swing-foot generator's on the robot's own plan; torso and
+ * base follow the mean of the feet's first three entries; angular position errors are Log(R_des R_cur'), world frame;
+ * rows 21..26 (the base dofs of the joint task) are 0.  A robot whose scene_id is outside [0, S), whose t is outside
+ * [0, T[s]), whose step_idx + 1 >= n_steps[s], or with a non-finite word in an input row (of plan_pos: the entries in use)
+ * gets NaN in every output and touches no other robot; the checks are made before any table is read with that index.
+ *
+ * cmpc_walk_integrate: DEVICE pointers.  With R = Exp(q[0:3]):
+ *   v+ = v + dt qdd;  R+ = R Exp(dt v+[0:3]);  p+ = p + dt R v+[3:6];  q+[0:3] = Log(R+), angle <= pi;  q+[6:] = q[6:] + dt v+[6:]
+ * A robot with hold[b] != 0 (hold may be NULL) or a non-finite word in q, v or qdd keeps (q, v) bit for bit.
+ * q_out == q and v_out == v (in place) are allowed.
+ *
+ * Both launches are asynchronous on `stream` (hipStream_t; NULL = default stream), allocate nothing and do not synchronise
+ * the host.  Every function returns 0 on success; message via cmpc_walk_last_error.
+ */
+#ifndef CMPC_WALK_H
+#define CMPC_WALK_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define CMPC_WALK_ROWS 51        /* CMPC_WBC_TASK_ROWS + CMPC_WBC_DOFS */
+#define CMPC_WALK_FEET_WORDS 36
+
+typedef struct cmpc_walk_gait cmpc_walk_gait;
+
+int cmpc_walk_gait_create(int device, int32_t S, int32_t T_max, int32_t n_steps_max, const int32_t *T, const int32_t *step_idx,
+                          const int32_t *n_steps, const int32_t *step_start, const int32_t *ss_dur, const uint8_t *support_l,
+                          const double *ang, const double *init_feet, double step_height, double delta, cmpc_walk_gait **out);
+int cmpc_walk_gait_destroy(cmpc_walk_gait *gait);
+
+int cmpc_walk_task_refs(const cmpc_walk_gait *gait, int32_t B, const int32_t *t, const int32_t *scene_id, const double *plan_pos,
+                        const double *pose, const double *vel, const double *jdqd, const double *com_des, const double *q,
+                        const double *v, const double *q_ref, double *ff, double *pos_err, double *vel_err, double *feet_des,
+                        void *stream);
+
+int cmpc_walk_integrate(int device, int32_t B, const double *q, const double *v, const double *qdd, double dt,
+                        const uint8_t *hold, double *q_out, double *v_out, void *stream);
+
+const char *cmpc_walk_last_error(void);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* CMPC_WALK_H */

@@ -27,6 +27,10 @@ WBC_SYMBOLS = ("cmpc_wbc_qp_solve_batch", "cmpc_wbc_qp_solve_tasks", "cmpc_wbc_d
 #: every symbol include/cmpc_rbd.h declares (batched rigid-body model, same library)
 RBD_SYMBOLS = ("cmpc_rbd_model_create", "cmpc_rbd_model_destroy", "cmpc_rbd_eval", "cmpc_rbd_last_error")
 
+#: every symbol include/cmpc_walk.h declares (task references and state integrator of the walking loop, same library)
+WALK_SYMBOLS = ("cmpc_walk_gait_create", "cmpc_walk_gait_destroy", "cmpc_walk_task_refs", "cmpc_walk_integrate",
+                "cmpc_walk_last_error")
+
 
 class WbcGains(ctypes.Structure):
     """``cmpc_wbc_gains`` of include/cmpc_wbc.h; task order lfoot, rfoot, com, torso, base, joints."""
@@ -111,6 +115,16 @@ def load():
     lib.cmpc_rbd_eval.restype = ctypes.c_int
     lib.cmpc_rbd_last_error.argtypes = []
     lib.cmpc_rbd_last_error.restype = ctypes.c_char_p
+    lib.cmpc_walk_gait_create.argtypes = [ctypes.c_int, i32, i32, i32] + [vp] * 8 + [f64, f64, ctypes.POINTER(vp)]
+    lib.cmpc_walk_gait_create.restype = ctypes.c_int
+    lib.cmpc_walk_gait_destroy.argtypes = [vp]
+    lib.cmpc_walk_gait_destroy.restype = ctypes.c_int
+    lib.cmpc_walk_task_refs.argtypes = [vp, i32] + [vp] * 15
+    lib.cmpc_walk_task_refs.restype = ctypes.c_int
+    lib.cmpc_walk_integrate.argtypes = [ctypes.c_int, i32, vp, vp, vp, f64, vp, vp, vp, vp]
+    lib.cmpc_walk_integrate.restype = ctypes.c_int
+    lib.cmpc_walk_last_error.argtypes = []
+    lib.cmpc_walk_last_error.restype = ctypes.c_char_p
     lib.cmpc_version.argtypes = []
     lib.cmpc_version.restype = ctypes.c_char_p
     _lib = lib

@@ -5,7 +5,9 @@ one HIP launch, in the layouts ``BatchedInverseDynamicsQP.solve_tasks`` and ``Ba
 
 ``RobotModel`` is the host side (numpy and the standard library): a kinematic tree parsed from a URDF, fixed joints merged,
 validated so that no table can index outside the kernel's arrays.  ``BatchedRobot`` is the device side; there is no CPU
-fallback.
+fallback.  ``Gait``, ``BatchedRobot.task_references``, ``integrate`` and ``walking_model`` close the loop around it
+(include/cmpc_walk.h, csrc/rbd_walk_kernel.hpp): the task references of a walking robot from its own adapted plan, and the
+step from the QP's acceleration to the next tick's (q, v).
 
 Coordinates (this build's own: parity with DART's is not pinned by any test): q[0:3] is the rotation
 vector of the base, R_b = Exp(q[0:3]) (world <- base), q[3:6] the base origin in the world, q[6+k] the joint angles in URDF
@@ -33,6 +35,10 @@ HRP4_INITIAL_DEG = {'CHEST_P': 0., 'CHEST_Y': 0., 'NECK_P': 0., 'NECK_Y': 0.,
                     'L_SHOULDER_P': 4., 'L_SHOULDER_R': 8., 'L_SHOULDER_Y': 0., 'L_ELBOW_P': -25.}
 
 Evaluation = collections.namedtuple("Evaluation", "J jdqd M h pose vel centroid")
+#: the outputs of ``cmpc_walk_task_refs``: rows of ``solve_tasks`` (21 task rows + 30 dofs), and the desired feet
+NACC, FEET_WORDS = ROWS + DOFS, 36
+References = collections.namedtuple("References", "ff pos_err vel_err feet_des")
+REFERENCE_FIELDS = References._fields
 
 
 def rpy_matrix(rpy):
@@ -330,3 +336,150 @@ class BatchedRobot:
 
         model.last_evaluation = None
         return model
+
+    # ---- the walking loop (include/cmpc_walk.h) ----------------------------------------------------------------------------
+    def _checked(self, name, t, shape, dtype=None):
+        import torch
+        dtype = torch.float64 if dtype is None else dtype
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)
+                and t.device == self.device):
+            raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {tuple(shape)} on {self.device}")
+        return t
+
+    def task_references(self, gait, t, scene_id, plan_pos, ev, com_des, q, v, q_ref=None, outputs=REFERENCE_FIELDS):
+        """One launch of ``cmpc_walk_task_refs``: the ``solve_tasks`` inputs of a walking robot.  t (B,) int32 and scene_id
+        (B,) int32 or None (scene 0); plan_pos (B, n_steps_max, 3), every robot's own plan; ev: an ``Evaluation`` with pose,
+        vel and jdqd; com_des (B,9) = desired CoM position, velocity, acceleration; q, v (B,30); q_ref (30,) the posture the
+        joint task holds (None: zeros).  Returns ``References(ff, pos_err, vel_err (B,51), feet_des (B,36))`` on the
+        current stream; fields not in ``outputs`` are None (the kernel skips them)."""
+        import torch
+        if not isinstance(gait, Gait) or gait.device != self.device:
+            raise ValueError(f"gait must be a rbd.Gait on {self.device}")
+        B = q.shape[0]
+        self._checked("t", t, (B,), torch.int32)
+        if scene_id is not None:
+            self._checked("scene_id", scene_id, (B,), torch.int32)
+        self._checked("plan_pos", plan_pos, (B, gait.n_steps_max, 3))
+        for name in ("pose", "vel", "jdqd"):
+            self._checked("ev." + name, getattr(ev, name), (B, ROWS))
+        self._checked("com_des", com_des, (B, 9))
+        self._checked("q", q, (B, DOFS))
+        self._checked("v", v, (B, DOFS))
+        if q_ref is not None:
+            self._checked("q_ref", q_ref, (DOFS,))
+        unknown = set(outputs) - set(REFERENCE_FIELDS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        out = {k: (torch.empty((B, FEET_WORDS if k == "feet_des" else NACC), dtype=torch.float64, device=self.device)
+                   if k in outputs else None) for k in REFERENCE_FIELDS}
+        if B > 0:
+            ptr = lambda x: None if x is None else x.data_ptr()
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self._lib.cmpc_walk_task_refs(gait._handle, B, t.data_ptr(), ptr(scene_id), plan_pos.data_ptr(), ev.pose.data_ptr(),
+                                               ev.vel.data_ptr(), ev.jdqd.data_ptr(), com_des.data_ptr(), q.data_ptr(), v.data_ptr(),
+                                               ptr(q_ref), *(ptr(out[k]) for k in REFERENCE_FIELDS), ctypes.c_void_p(stream))
+            if rc != 0:
+                raise RuntimeError(self._lib.cmpc_walk_last_error().decode())
+        return References(**out)
+
+    def integrate(self, q, v, qdd, dt, hold=None, out=None):
+        """One launch of ``cmpc_walk_integrate``: (q, v) (B,30) advanced by dt with the acceleration qdd (B,30) in the
+        body-twist convention of this module.  hold (B,) uint8 / bool: rows that keep (q, v); a row with a non-finite word
+        keeps them too.  out: (q_out, v_out), which may be (q, v) themselves; None allocates.  Returns (q_out, v_out)."""
+        import torch
+        B = q.shape[0]
+        for name, x in (("q", q), ("v", v), ("qdd", qdd)):
+            self._checked(name, x, (B, DOFS))
+        if hold is not None:
+            if torch.is_tensor(hold) and hold.dtype == torch.bool:
+                hold = hold.view(torch.uint8)                     # (same bytes: True is 1)
+            self._checked("hold", hold, (B,), torch.uint8)
+        q_out, v_out = (torch.empty_like(q), torch.empty_like(v)) if out is None else out
+        self._checked("q_out", q_out, (B, DOFS))
+        self._checked("v_out", v_out, (B, DOFS))
+        if B > 0:
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self._lib.cmpc_walk_integrate(self.device.index, B, q.data_ptr(), v.data_ptr(), qdd.data_ptr(), float(dt),
+                                               None if hold is None else hold.data_ptr(), q_out.data_ptr(), v_out.data_ptr(),
+                                               ctypes.c_void_p(stream))
+            if rc != 0:
+                raise RuntimeError(self._lib.cmpc_walk_last_error().decode())
+        return q_out, v_out
+
+    def walking_model(self, q, v, gait, q_ref=None, integrate=True, redundant_dofs=HRP4_REDUNDANT_DOFS):
+        """A callable for ``BatchedRollout.attach_whole_body_tasks(qp, model)`` that walks: per tick it evaluates the
+        kernel at (q, v), forms every task reference from the robot's own adapted plan (``task_references`` on the
+        rollout's ``t``, ``scene_id`` and ``plan_pos``, the CoM rows from the MPC's ``desired``) and returns the
+        ``solve_tasks`` inputs.  Its ``advance(rollout, last_wbc)``, which the rollout calls after the QP, integrates
+        q, v in place by the QP's acceleration with dt = the spec's delta; a robot whose QP failed or that is no
+        longer alive holds.  q_ref (30,): the posture of the joint task (None: the first robot's q now).
+        ``integrate=False`` leaves q, v to the caller.  ``last_evaluation`` and ``last_references`` keep the tick's."""
+        import torch
+        sel = torch.from_numpy(self.model.joint_selection(redundant_dofs)).to(self.device)
+        q_ref = q[0].clone() if q_ref is None else q_ref
+
+        def model(rollout, desired):
+            ev = self.evaluate(q, v)
+            com_des = torch.cat([desired["com_pos"], desired["com_vel"], desired["com_acc"]], dim=1).contiguous()
+            refs = self.task_references(gait, rollout.t, getattr(rollout, "scene_id", None), rollout.plan_pos, ev, com_des, q, v, q_ref)
+            model.last_evaluation, model.last_references = ev, refs
+            return ev.J, None, refs.ff, refs.pos_err, refs.vel_err, None, ev.M, ev.h, sel
+
+        def advance(rollout, last_wbc):
+            hold = (last_wbc[3] != 0) | ~rollout.alive
+            self.integrate(q, v, last_wbc[1], rollout.spec.delta, hold=hold, out=(q, v))
+
+        model.last_evaluation = model.last_references = None
+        if integrate:
+            model.advance = advance
+        return model
+
+
+class Gait:
+    """The gait tables of a ``workloads.Scene`` or ``SceneSet`` on the GPU (``cmpc_walk_gait_create``): what
+    ``BatchedRobot.task_references`` reads of the walk besides every robot's own plan positions.  ``tables``: the dict of
+    ``gait_tables()`` instead of a scene.  A malformed table is refused with the native validation's message."""
+
+    def __init__(self, scene_or_set=None, device="cuda:0", tables=None):
+        import torch
+        from . import capi
+        if not torch.cuda.is_available():
+            raise RuntimeError("Gait needs a ROCm GPU: there is no CPU fallback")
+        self.device = torch.device(device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if (scene_or_set is None) == (tables is None):
+            raise ValueError("Gait takes a Scene or SceneSet, or the dict of its gait_tables(), not both")
+        self.tables = gait_arguments(scene_or_set.gait_tables() if tables is None else tables)
+        self.S, self.T_max, self.n_steps_max = self.tables[:3]
+        self._lib = capi.load()
+        self._handle = ctypes.c_void_p()
+        rc = self._lib.cmpc_walk_gait_create(self.device.index, *(a.ctypes.data if isinstance(a, np.ndarray) else a for a in self.tables),
+                                             ctypes.byref(self._handle))
+        if rc != 0:
+            raise ValueError(self._lib.cmpc_walk_last_error().decode())
+
+    def __del__(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        if h:
+            self._lib.cmpc_walk_gait_destroy(h)
+
+
+def gait_arguments(tab):
+    """The dict of ``gait_tables()`` as the arguments of ``cmpc_walk_gait_create`` after the device: (S, T_max,
+    n_steps_max, T, step_idx, n_steps, step_start, ss_dur, support_l, ang, init_feet, step_height, delta), the arrays
+    contiguous in the ABI's types.  Shapes are checked here; the values by the native validation."""
+    T = np.ascontiguousarray(tab['T'], dtype=np.int32)
+    step_idx = np.ascontiguousarray(tab['step_idx'], dtype=np.int32)
+    step_start = np.ascontiguousarray(tab['step_start'], dtype=np.int32)
+    if T.ndim != 1 or step_idx.ndim != 2 or step_start.ndim != 2:
+        raise ValueError("gait tables: T (S,), step_idx (S, T_max), step_start (S, n_steps_max)")
+    S, Tm, nm = T.shape[0], step_idx.shape[1], step_start.shape[1]
+    arrays = (T, step_idx, np.ascontiguousarray(tab['n_steps'], dtype=np.int32), step_start,
+              np.ascontiguousarray(tab['ss_dur'], dtype=np.int32), np.ascontiguousarray(tab['support_l'], dtype=np.uint8),
+              np.ascontiguousarray(tab['ang'], dtype=np.float64), np.ascontiguousarray(tab['init_feet'], dtype=np.float64))
+    for a, shape, name in zip(arrays, ((S,), (S, Tm), (S,), (S, nm), (S, nm), (S, nm), (S, nm, 3), (S, 12)),
+                              ('T', 'step_idx', 'n_steps', 'step_start', 'ss_dur', 'support_l', 'ang', 'init_feet')):
+        if a.shape != shape:
+            raise ValueError(f"gait tables: {name} must have shape {shape}, got {a.shape}")
+    return (S, Tm, nm) + arrays + (float(tab['step_height']), float(tab['delta']))

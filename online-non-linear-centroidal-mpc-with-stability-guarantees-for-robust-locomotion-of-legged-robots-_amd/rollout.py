@@ -156,6 +156,8 @@ class BatchedRollout:
         contact = torch.stack([desired["gamma_l"], desired["gamma_r"]], dim=1).to(torch.float64).contiguous()
         mu = self.state[:, 15].contiguous() if tasks["mu"] is None else tasks["mu"]
         self.last_wbc = qp.solve_tasks(*args[:8], contact, mu, tasks["foot_size"], *args[8:])
+        if hasattr(model, "advance"):                      # (``BatchedRobot.walking_model``: q, v move by the QP's acceleration)
+            model.advance(self, self.last_wbc)
 
     def desired_com(self, x1, u0, t):
         """``model_state['com']`` of the reference's back half (:633-649) for the batch: position and velocity of x_1 and

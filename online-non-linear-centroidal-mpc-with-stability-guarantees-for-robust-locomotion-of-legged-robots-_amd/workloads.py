@@ -88,6 +88,11 @@ class Scene:
     def t_max(self, N, rate=1):
         return self.T - 1 - (N + 1) * rate
 
+    def gait_tables(self):
+        """The host tables of ``cmpc_walk_gait_create`` (include/cmpc_walk.h) for this walk, S = 1: what the swing-foot
+        generator reads from the planner at a tick, except the plan positions, which every robot of a rollout owns."""
+        return _gait_tables([self])
+
     def build_records(self, spec, t, com, dcom, hw, theta_hat, yaw_l, yaw_r, mass, mu, rate=1):
         """Vectorised front half of ``solve`` for B instances.  All inputs have leading dim B."""
         t = np.asarray(t, dtype=np.int64)
@@ -115,6 +120,32 @@ class Scene:
         com = np.stack([self.com_tab[t, 0], self.com_tab[t, 1], np.full(t.shape, 0.72)], axis=1)
         dcom = np.stack([self.com_tab[t, 3], self.com_tab[t, 4], np.zeros(t.shape)], axis=1)
         return com, dcom
+
+
+def _gait_tables(scenes):
+    """dict of the gait tables of S scenes, padded per scene (-1 for the integers, 0 for support_l, NaN for ang): T (S,),
+    step_idx (S, T_max) int32, n_steps (S,), step_start / ss_dur (S, n_steps_max) int32 ticks, support_l (S, n_steps_max)
+    uint8, ang (S, n_steps_max, 3), init_feet (S, 12) = [lfoot ang, pos, rfoot ang, pos], step_height, delta."""
+    S = len(scenes)
+    for k in ('step_height', 'world_time_step'):
+        if any(sc.params[k] != scenes[0].params[k] for sc in scenes):
+            raise ValueError(f"all scenes of a gait must share params[{k!r}]")
+    T = np.array([sc.T for sc in scenes], dtype=np.int32)
+    n = np.array([len(sc.planner.plan) for sc in scenes], dtype=np.int32)
+    Tm, nm = int(T.max()), int(n.max())
+    tab = dict(T=T, n_steps=n, step_idx=np.full((S, Tm), -1, np.int32), step_start=np.full((S, nm), -1, np.int32),
+               ss_dur=np.full((S, nm), -1, np.int32), support_l=np.zeros((S, nm), np.uint8), ang=np.full((S, nm, 3), np.nan),
+               init_feet=np.zeros((S, 12)), step_height=float(scenes[0].params['step_height']),
+               delta=float(scenes[0].params['world_time_step']))
+    for s, sc in enumerate(scenes):
+        pl = sc.planner
+        tab['step_idx'][s, :T[s]] = sc.step_idx[:T[s]]
+        tab['step_start'][s, :n[s]] = pl.step_end_times() - np.array([p['ss_duration'] + p['ds_duration'] for p in pl.plan])
+        tab['ss_dur'][s, :n[s]] = pl.ss_durations()
+        tab['support_l'][s, :n[s]] = pl.support_is_left()
+        tab['ang'][s, :n[s]] = np.array([p['ang'] for p in pl.plan], dtype=np.float64)
+        tab['init_feet'][s] = np.hstack((sc.initial['lfoot']['pos'], sc.initial['rfoot']['pos']))
+    return tab
 
 
 def rollout_schedule(sc, N, rate=1):
@@ -173,6 +204,10 @@ class SceneSet:
     def t_max(self, N, rate=1):
         """Last valid tick of every scene, (S,)."""
         return self.T - 1 - (N + 1) * rate
+
+    def gait_tables(self):
+        """The host tables of ``cmpc_walk_gait_create`` for the S walks, padded per scene (``Scene.gait_tables``)."""
+        return _gait_tables(self.scenes)
 
     def build_records(self, spec, t, scene_id, com, dcom, hw, theta_hat, yaw_l, yaw_r, mass, mu, rate=1):
         """``Scene.build_records`` for a mixed batch: instance b is tick t[b] of scene scene_id[b]."""
