@@ -34,7 +34,25 @@
  * A robot with hold[b] != 0 (hold may be NULL) or a non-finite word in q, v or qdd keeps (q, v) bit for bit.
  * q_out == q and v_out == v (in place) are allowed.
  *
- * Both launches are asynchronous on `stream` (hipStream_t; NULL = default stream), allocate nothing and do not synchronise
+ * cmpc_walk_measure: DEVICE pointers, instance-major: the measured x_0 of the MPC (code/simulation.py:201-204 and
+ * code/centroidal_mpc_vertices.py:482-489 of the reference) from the robot's own evaluation.
+ *   centroid [B][9], pose [B][21]   of cmpc_rbd_eval
+ *   state [B][16]                   the rollout's [com dcom hw theta_hat yaw_l yaw_r mass mu], updated in place
+ *   alive [B] uint8                 updated in place (NULL: every robot counts as alive, nothing is written)
+ *   x_meas [B][20], innovation [B][9]   optional outputs (NULL = skipped)
+ * Per robot, every input is read before any word is written.  dead = alive && alive[b] == 0; bad = a non-finite word among
+ * the 30 of centroid[b] and pose[b]; fallen = !(centroid[b][2] > z_min) || !(R22 > cos_tilt_min), R22 the last entry of
+ * Exp(pose[b][18:21]), the cosine of the base's tilt from the vertical (-INFINITY disables a guard).
+ *   dead             state[b], alive[b] keep their bits; the rows of x_meas and innovation are NaN
+ *   bad or fallen    state[b] keeps its bits, alive[b] = 0; both rows are NaN
+ *   otherwise        innovation[b] = centroid[b] - state[b][0:9] (measured minus predicted, from the old state);
+ *                    state[b][0:9] = centroid[b]; state[b][12] = pose[b][2]; state[b][13] = pose[b][8] (the third angle of
+ *                    each foot pose); theta_hat, mass and mu are not touched;
+ *                    x_meas[b] = [centroid 9, state[9:12], pose[2], pose[3], pose[4], 0, pose[8], pose[9], pose[10], 0],
+ *                    the x_meas of cmpc_gain_track
+ * No robot's row touches another robot's.  B < 0, a NaN z_min or cos_tilt_min and a null centroid, pose or state are refused.
+ *
+ * The launches are asynchronous on `stream` (hipStream_t; NULL = default stream), allocate nothing and do not synchronise
  * the host.  Every function returns 0 on success; message via cmpc_walk_last_error.
  */
 #ifndef CMPC_WALK_H
@@ -63,6 +81,9 @@ int cmpc_walk_task_refs(const cmpc_walk_gait *gait, int32_t B, const int32_t *t,
 
 int cmpc_walk_integrate(int device, int32_t B, const double *q, const double *v, const double *qdd, double dt,
                         const uint8_t *hold, double *q_out, double *v_out, void *stream);
+
+int cmpc_walk_measure(int device, int32_t B, const double *centroid, const double *pose, double z_min, double cos_tilt_min,
+                      double *state, uint8_t *alive, double *x_meas, double *innovation, void *stream);
 
 const char *cmpc_walk_last_error(void);
 

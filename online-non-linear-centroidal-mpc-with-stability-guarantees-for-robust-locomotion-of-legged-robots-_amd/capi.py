@@ -29,7 +29,7 @@ RBD_SYMBOLS = ("cmpc_rbd_model_create", "cmpc_rbd_model_destroy", "cmpc_rbd_eval
 
 #: every symbol include/cmpc_walk.h declares (task references and state integrator of the walking loop, same library)
 WALK_SYMBOLS = ("cmpc_walk_gait_create", "cmpc_walk_gait_destroy", "cmpc_walk_task_refs", "cmpc_walk_integrate",
-                "cmpc_walk_last_error")
+                "cmpc_walk_measure", "cmpc_walk_last_error")
 
 
 class WbcGains(ctypes.Structure):
@@ -123,6 +123,8 @@ def load():
     lib.cmpc_walk_task_refs.restype = ctypes.c_int
     lib.cmpc_walk_integrate.argtypes = [ctypes.c_int, i32, vp, vp, vp, f64, vp, vp, vp, vp]
     lib.cmpc_walk_integrate.restype = ctypes.c_int
+    lib.cmpc_walk_measure.argtypes = [ctypes.c_int, i32, vp, vp, f64, f64, vp, vp, vp, vp, vp]
+    lib.cmpc_walk_measure.restype = ctypes.c_int
     lib.cmpc_walk_last_error.argtypes = []
     lib.cmpc_walk_last_error.restype = ctypes.c_char_p
     lib.cmpc_version.argtypes = []

@@ -157,4 +157,7 @@ int cmpc_walk_integrate(int device, int32_t B, const double *q, const double *v,
 
 const char *cmpc_walk_last_error(void) { return g_walk_err.c_str(); }
 
+// for the library's other walking-loop unit (csrc/walk_measure.hip): not part of include/cmpc_walk.h
+void cmpc_walk_set_error(const char *msg) { g_walk_err = msg ? msg : ""; }
+
 }  // extern "C"

@@ -7,7 +7,8 @@ one HIP launch, in the layouts ``BatchedInverseDynamicsQP.solve_tasks`` and ``Ba
 validated so that no table can index outside the kernel's arrays.  ``BatchedRobot`` is the device side; there is no CPU
 fallback.  ``Gait``, ``BatchedRobot.task_references``, ``integrate`` and ``walking_model`` close the loop around it
 (include/cmpc_walk.h, csrc/rbd_walk_kernel.hpp): the task references of a walking robot from its own adapted plan, and the
-step from the QP's acceleration to the next tick's (q, v).
+step from the QP's acceleration to the next tick's (q, v).  ``BatchedRobot.measure`` (``cmpc_walk_measure``,
+csrc/walk_measure_kernel.hpp) feeds the robot's own centroid and foot angles back into the state its MPC starts from.
 
 Coordinates (this build's own: parity with DART's is not pinned by any test): q[0:3] is the rotation
 vector of the base, R_b = Exp(q[0:3]) (world <- base), q[3:6] the base origin in the world, q[6+k] the joint angles in URDF
@@ -39,6 +40,8 @@ Evaluation = collections.namedtuple("Evaluation", "J jdqd M h pose vel centroid"
 NACC, FEET_WORDS = ROWS + DOFS, 36
 References = collections.namedtuple("References", "ff pos_err vel_err feet_des")
 REFERENCE_FIELDS = References._fields
+#: the optional outputs of ``cmpc_walk_measure``: the measured x0 (B,20) and measured minus predicted (B,9)
+Measurement = collections.namedtuple("Measurement", "x_meas innovation")
 
 
 def rpy_matrix(rpy):
@@ -406,20 +409,65 @@ class BatchedRobot:
                 raise RuntimeError(self._lib.cmpc_walk_last_error().decode())
         return q_out, v_out
 
-    def walking_model(self, q, v, gait, q_ref=None, integrate=True, redundant_dofs=HRP4_REDUNDANT_DOFS):
+    def measure(self, ev, state, alive=None, z_min=-np.inf, tilt_max=None, outputs=Measurement._fields):
+        """One launch of ``cmpc_walk_measure``: the robot's own centroid (``ev.centroid`` (B,9): CoM, its velocity, the
+        angular momentum about it) and the third angle of each foot pose (``ev.pose`` (B,21)) become words 0..8, 12 and 13
+        of ``state`` (B,16), the rollout's state, in place.  A robot with ``alive[b] == 0`` (alive (B,) bool / uint8, or
+        None: all alive) keeps its state; one with a non-finite word in its evaluation, with its CoM not above ``z_min`` or
+        its base tilted past ``tilt_max`` (radians; None: no limit) keeps its state too and ``alive[b]`` becomes 0.
+        Returns ``Measurement(x_meas (B,20), innovation (B,9))`` on the current stream: the measured x0 in the layout
+        ``BatchedRollout.track`` takes, and measured minus the state's words 0..8 as they were; the rows of robots that
+        were not measured are NaN, fields not in ``outputs`` are None (the kernel skips them)."""
+        import torch
+        B = state.shape[0]
+        self._checked("ev.centroid", ev.centroid, (B, 9))
+        self._checked("ev.pose", ev.pose, (B, ROWS))
+        self._checked("state", state, (B, 16))
+        if alive is not None:
+            if torch.is_tensor(alive) and alive.dtype == torch.bool:
+                alive = alive.view(torch.uint8)                   # (same bytes: True is 1, and the kernel writes 0)
+            self._checked("alive", alive, (B,), torch.uint8)
+        unknown = set(outputs) - set(Measurement._fields)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        cos_tilt_min = -np.inf if tilt_max is None else float(np.cos(tilt_max))
+        out = {k: (torch.empty((B, 20 if k == "x_meas" else 9), dtype=torch.float64, device=self.device) if k in outputs else None)
+               for k in Measurement._fields}
+        ptr = lambda x: None if x is None else x.data_ptr()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        rc = self._lib.cmpc_walk_measure(self.device.index, B, ev.centroid.data_ptr(), ev.pose.data_ptr(), float(z_min), cos_tilt_min,
+                                         state.data_ptr(), ptr(alive), ptr(out["x_meas"]), ptr(out["innovation"]),
+                                         ctypes.c_void_p(stream))
+        if rc != 0:
+            raise RuntimeError(self._lib.cmpc_walk_last_error().decode())
+        return Measurement(**out)
+
+    def walking_model(self, q, v, gait, q_ref=None, integrate=True, redundant_dofs=HRP4_REDUNDANT_DOFS, fall=None):
         """A callable for ``BatchedRollout.attach_whole_body_tasks(qp, model)`` that walks: per tick it evaluates the
         kernel at (q, v), forms every task reference from the robot's own adapted plan (``task_references`` on the
         rollout's ``t``, ``scene_id`` and ``plan_pos``, the CoM rows from the MPC's ``desired``) and returns the
         ``solve_tasks`` inputs.  Its ``advance(rollout, last_wbc)``, which the rollout calls after the QP, integrates
         q, v in place by the QP's acceleration with dt = the spec's delta; a robot whose QP failed or that is no
         longer alive holds.  q_ref (30,): the posture of the joint task (None: the first robot's q now).
-        ``integrate=False`` leaves q, v to the caller.  ``last_evaluation`` and ``last_references`` keep the tick's."""
+        ``integrate=False`` leaves q, v to the caller.  ``last_evaluation`` and ``last_references`` keep the tick's.
+        Its ``measure(rollout)``, with which a rollout built with ``feedback=True`` begins its tick, evaluates (q, v) and
+        launches ``measure`` on the rollout's ``state`` and ``alive`` (fall = (z_min, tilt_max): the guards of ``measure``);
+        the result is kept as ``last_measurement``, and the same tick's ``model(rollout, desired)`` uses that evaluation
+        instead of launching a second one."""
         import torch
         sel = torch.from_numpy(self.model.joint_selection(redundant_dofs)).to(self.device)
         q_ref = q[0].clone() if q_ref is None else q_ref
+        z_min, tilt_max = (-np.inf, None) if fall is None else fall
+        measured = []                                             # the evaluation of a tick that began with measure()
+
+        def measure(rollout):
+            ev = self.evaluate(q, v)
+            model.last_measurement = self.measure(ev, rollout.state, rollout.alive, z_min=z_min, tilt_max=tilt_max)
+            measured[:] = [ev]
+            return model.last_measurement
 
         def model(rollout, desired):
-            ev = self.evaluate(q, v)
+            ev = measured.pop() if measured else self.evaluate(q, v)
             com_des = torch.cat([desired["com_pos"], desired["com_vel"], desired["com_acc"]], dim=1).contiguous()
             refs = self.task_references(gait, rollout.t, getattr(rollout, "scene_id", None), rollout.plan_pos, ev, com_des, q, v, q_ref)
             model.last_evaluation, model.last_references = ev, refs
@@ -429,7 +477,8 @@ class BatchedRobot:
             hold = (last_wbc[3] != 0) | ~rollout.alive
             self.integrate(q, v, last_wbc[1], rollout.spec.delta, hold=hold, out=(q, v))
 
-        model.last_evaluation = model.last_references = None
+        model.last_evaluation = model.last_references = model.last_measurement = None
+        model.measure = measure
         if integrate:
             model.advance = advance
         return model

@@ -25,6 +25,15 @@ momentum lookup stays a torch gather.  With ``consts`` every instance is solved 
 (``solve_with_consts``), with one scene or with a set.  With ``gains=True`` every tick also returns the first-stage gains
 (``solve_with_gain``, with the instances' own constants when there are any; the trajectory is the same bit for bit) and
 ``track`` applies them to a measured state between two solves.
+
+With ``feedback=True`` the loop is closed around the robot of the attached ``BatchedRobot.walking_model``: every tick begins
+with ``model.measure(self)`` (``cmpc_walk_measure``), which puts the robot's own centroid -- CoM, its velocity, the angular
+momentum about it -- and foot angles into the state the records are built from, as the reference's ``retrieve_state`` does
+first in ``customPreStep`` (code/simulation.py:201-204).  The order of the tick is then: measure, records from the measured
+state, MPC solve, task references and QP on the same evaluation, integrate.  Step 3 is unchanged: words 0..11 of the state
+are the MPC's prediction x_1 until the next measurement replaces words 0..8 (``last_measurement.innovation`` is their
+difference); theta_hat carries over from x_1.  A robot whose evaluation is not finite or that has fallen stops exactly as
+one whose solve failed.
 """
 import numpy as np
 import torch
@@ -50,12 +59,18 @@ def _checked_consts(consts, spec, B):
 
 class BatchedRollout:
     def __init__(self, scene, spec, B, device="cuda:0", mass=None, mu=0.5, update_contact=True,
-                 hw_measured=None, hw_offset=None, rate=1, scene_id=None, consts=None, gains=False):
+                 hw_measured=None, hw_offset=None, rate=1, scene_id=None, consts=None, gains=False, feedback=False):
         """scene: a ``workloads.Scene`` (one walk for the batch) or a ``workloads.SceneSet`` with ``scene_id`` (B,) naming
         every instance's walk (optional for a set of one).  hw_measured: one recording (ticks, 3), or with a set one per
         scene.  consts (B, 18): per-instance problem constants, every row with the spec's delta.
         gains: every tick solves through ``solve_with_gain`` and keeps ``last_gain`` (B, 20 + nu, 20) next to
-        ``last_records`` and ``last_XU`` (``track``); it is one buffer, overwritten by the next tick."""
+        ``last_records`` and ``last_XU`` (``track``); it is one buffer, overwritten by the next tick.
+        feedback: every tick begins with the attached model's ``measure`` (the module's docstring) and keeps
+        ``last_measurement`` next to ``last_records``; the robot's own momentum is the signal, so ``hw_measured`` and
+        ``hw_offset`` are refused with it, and so is a ``push_dv``."""
+        if feedback and (hw_measured is not None or hw_offset is not None):
+            raise ValueError("feedback=True takes the angular momentum from the robot itself: hw_measured and hw_offset do not go with it")
+        self.feedback, self.last_measurement = bool(feedback), None
         consts = None if consts is None else _checked_consts(consts, spec, B)
         self._set = scene if isinstance(scene, SceneSet) else None
         if self._set is None and scene_id is not None:
@@ -181,7 +196,20 @@ class BatchedRollout:
         h = self.hw_measured[torch.clamp(t.long(), max=self.hw_measured.shape[0] - 1)]
         return h if self.hw_offset is None else h + self.hw_offset
 
+    def _measure(self, push_dv):
+        """The head of a tick with ``feedback``: the attached model's measurement into ``state`` and ``alive``."""
+        if push_dv is not None:
+            raise ValueError("push_dv does not go with feedback=True: the next measurement would overwrite it; disturb the robot "
+                             "through its own q, v")
+        model = None if self._wbc is None else self._wbc[1]
+        if not hasattr(model, "measure"):
+            raise RuntimeError("feedback=True needs an attached model with a measure(rollout), such as BatchedRobot.walking_model "
+                               "(attach_whole_body_tasks)")
+        self.last_measurement = model.measure(self)
+
     def reset(self, t0, com, dcom, hw=None, theta_hat=None):
+        """Every instance at tick t0 with the given centroidal state, the scene's plan, no warm start, alive.  With
+        ``feedback`` the first measurement replaces com, dcom and hw by the robot's own."""
         dev, f64 = self.device, torch.float64
         self.t[:] = torch.as_tensor(t0, dtype=torch.int32, device=dev)
         self.state[:, 0:3] = torch.as_tensor(com, dtype=f64, device=dev)
@@ -223,6 +251,8 @@ class BatchedRollout:
     def _step_set(self, push_dv):
         """``step`` of a fleet: records by (scene, tick), the solve, then the back half in one launch."""
         sp, N, dev = self.spec, self.spec.N, self.device
+        if self.feedback:
+            self._measure(push_dv)
         rec = self.builder.build(sp, self.t, self.state, rate=self.rate, scene_id=self.scene_id,
                                  plan_pos=self.plan_pos if self.update_contact else None)
         s_in, s_out = self._state
@@ -246,6 +276,8 @@ class BatchedRollout:
         if self._set is not None:
             return self._step_set(push_dv)
         sp, N = self.spec, self.spec.N
+        if self.feedback:
+            self._measure(push_dv)
         rec = self.builder.build(sp, self.t, self.state, rate=self.rate,
                                  plan_pos=self.plan_pos if self.update_contact else None)
         s_in, s_out = self._state
@@ -285,6 +317,8 @@ class BatchedRollout:
     def run(self, ticks, push=None):
         """`ticks` control steps; push = (first_tick, last_tick, dv(3)) velocity disturbance per tick.
         Returns the CoM history (ticks+1, B, 3) and the final alive mask."""
+        if self.feedback and push is not None:
+            raise ValueError("push does not go with feedback=True: disturb the robot through its own q, v")
         hist = [self.state[:, 0:3].clone()]
         for i in range(ticks):
             dv = push[2] if (push is not None and push[0] <= i <= push[1]) else None
