@@ -26,9 +26,12 @@ RBD_DEPS = [os.path.join(CSRC, "rbd_kernel.hpp"), os.path.join(ROOT, "include", 
 WALK_DEPS = [os.path.join(CSRC, "rbd_walk_kernel.hpp"), os.path.join(ROOT, "include", "cmpc_walk.h")]
 # the device source of the measurement that closes that loop (cmpc_walk_measure), which tests/emu/walk_measure_emu.cpp compiles as well
 MEASURE_DEPS = [os.path.join(CSRC, "walk_measure_kernel.hpp"), os.path.join(ROOT, "include", "cmpc_walk.h")]
+# the device source of the contact plant (cmpc_walk_plant_step), which tests/emu/walk_plant_emu.cpp compiles as well
+PLANT_DEPS = [os.path.join(CSRC, "walk_plant_kernel.hpp"), os.path.join(CSRC, "rbd_walk_kernel.hpp"),
+              os.path.join(ROOT, "include", "cmpc_walk.h")]
 DEVICE_UNITS = [os.path.join(CSRC, "cmpc_hip.hip"), os.path.join(CSRC, "wbc_qp.hip"), os.path.join(CSRC, "rbd.hip"),
-                os.path.join(CSRC, "rbd_walk.hip"), os.path.join(CSRC, "walk_measure.hip")]
-DEVICE_DEPS = DEVICE_UNITS + KERNEL_DEPS + RBD_DEPS + WALK_DEPS + MEASURE_DEPS + [
+                os.path.join(CSRC, "rbd_walk.hip"), os.path.join(CSRC, "walk_measure.hip"), os.path.join(CSRC, "walk_plant.hip")]
+DEVICE_DEPS = DEVICE_UNITS + KERNEL_DEPS + RBD_DEPS + WALK_DEPS + MEASURE_DEPS + PLANT_DEPS + [
     os.path.join(CSRC, "cmpc_order_fit.h"), os.path.join(ROOT, "include", "cmpc_wbc.h")]
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 
@@ -154,6 +157,15 @@ def build_emu_walk_measure(force=False):
     return out
 
 
+def build_emu_walk_plant(force=False):
+    """Host emulation of the contact plant (tests/emu/walk_plant_emu.cpp, on the harness of rbd_emu.cpp): test harness only."""
+    src, out = os.path.join(EMU_DIR, "walk_plant_emu.cpp"), os.path.join(EMU_DIR, "libwalk_plant_emu.so")
+    if force or _newer(out, [src, os.path.join(EMU_DIR, "rbd_emu.cpp")] + RBD_DEPS + PLANT_DEPS):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-fPIC", "-shared", "-pthread",
+                               "-o", out, src])
+    return out
+
+
 def build_device_unit(force=False):
     """GPU-tier unit harness for the device-only primitives (tests/gpu_unit): never loaded by the package."""
     src = os.path.join(ROOT, "tests", "gpu_unit", "cmpc_device_unit.hip")
@@ -195,5 +207,6 @@ if __name__ == "__main__":
     print(build_emu_rbd(force))
     print(build_emu_rbd_walk(force))
     print(build_emu_walk_measure(force))
+    print(build_emu_walk_plant(force))
     print(build_device_unit(force))
     print(build_tools(force))

@@ -1,8 +1,9 @@
 /*
  * cmpc_walk.h -- C ABI of the walking loop around the batched rigid-body model (libcmpc_amd.so): the whole-body task
  * references of B robots from each robot's own adapted plan (code/simulation.py:227-231, :269-271 and
- * code/inverse_dynamics.py:68-89 of the reference) and the step that advances (q, v) by the whole-body QP's acceleration,
- * one launch each.  Coordinates and task rows are those of include/cmpc_rbd.h and include/cmpc_wbc.h.
+ * code/inverse_dynamics.py:68-89 of the reference), the step that advances (q, v) by the whole-body QP's acceleration, the
+ * measurement that feeds the robot back to its MPC and the contact plant that moves it by torques, ground and pushes, one
+ * launch each.  Coordinates and task rows are those of include/cmpc_rbd.h and include/cmpc_wbc.h.
  *
  * cmpc_walk_gait_create: HOST tables of S walks, row-major, padded per scene (padding is never read):
  *   T          [S]                  ticks of each scene, 1 <= T[s] <= T_max
@@ -52,6 +53,43 @@
  *                    the x_meas of cmpc_gain_track
  * No robot's row touches another robot's.  B < 0, a NaN z_min or cos_tilt_min and a null centroid, pose or state are refused.
  *
+ * cmpc_walk_plant_step: DEVICE pointers, instance-major: the contact plant.  Joint torques, a wrench on the base and a flat
+ * frictional floor under the eight sole vertices move the robot one tick (what the reference leaves to DART's world step,
+ * code/simulation.py:193-300): a velocity-level time-stepping scheme, the contact impulses by projected Gauss-Seidel.
+ *   q, v [B][30]; M [B][30][30], h [B][30], J [B][21][30], pose [B][21]   of cmpc_rbd_eval at that same (q, v)
+ *   tau       word j of row b (leading dimension tau_ld >= 24) is the torque of dof 6 + j; NULL = zero torques
+ *   ext [B][6]        world-frame moment, then world-frame force at the base origin; NULL = none.  With R = Exp(q[0:3]) the
+ *                     generalised force is [R'm; R'f; 0]
+ *   foot_mu [B][2]    half foot size d and the floor's friction mu (the layout of cmpc_wbc_qp_solve_tasks)
+ *   hold [B] uint8    may be NULL
+ *   impulse [B][24]   in/out: last tick's impulses as the warm start, written with this tick's (world x, y, z per vertex,
+ *                     N s); NULL = cold start, nothing returned
+ *   q_out, v_out [B][30] (== q, v allowed); status [B] int32 and residual [B] are optional (NULL = skipped)
+ * Vertex i = 4f + k belongs to foot f (0 left, 1 right); corner k has the signs (sx, sy) = (+,+), (+,-), (-,+), (-,-).
+ *   R_f = Exp(pose[6f:6f+3]);  p_f = pose[6f+3:6f+6];  r_i = R_f (sx d, sy d, 0);  phi_i = (p_f + r_i).z - ground_z
+ *   Jc[3i:3i+3] = J[6f+3:6f+6] - [r_i]x J[6f:6f+3]
+ *   v_free = v + dt M^-1 ([R'm; R'f; tau] - h);   Y = M^-1 Jc';   W = Jc Y + cfm I
+ *   c = Jc v_free;   c[3i+2] += (phi_i >= 0 ? phi_i : erp phi_i) / dt
+ *   p = the warm start made admissible: p_n <- max(0, p_n), then (p_x, p_y) scaled onto the disk of radius mu p_n
+ *   `sweeps` times, i = 0..7 in order:  p_n <- max(0, p_n - (W[n].p + c_n) / W[n][n]) for n = 3i+2;
+ *       p_a <- p_a - (W[a].p + c_a) / W[a][a] for a = 3i, 3i+1 (each with the p just updated);
+ *       (p_x, p_y) scaled onto the disk of radius mu p_n (to 0 when p_n = 0)
+ *   v+ = v_free + Y p;   q+ from (q, v+, dt) as in cmpc_walk_integrate
+ * All eight vertices are always in the problem; the cone is the circular one; the sweep count is fixed.
+ *   status 0  stepped
+ *          1  held (hold[b] != 0): (q, v) keep their bits, the rows of impulse and residual are not touched
+ *          2  refused: (q, v) keep their bits, the impulse row is zeros, residual is NaN -- a non-finite word in an input
+ *             row of the robot (the warm start included), a foot_mu entry that is not finite and > 0, or a Cholesky pivot
+ *             of M that is not finite and > 0
+ *   residual  max_i max(0, -(W p + c)[3i+2]) after the last sweep: the normal velocity, in m/s, by which the step still
+ *             violates non-penetration
+ * Per robot every input is read before any word is written, and no robot's row touches another robot's.  Refused before the
+ * launch: B < 0; a null q, v, M, h, J, pose, foot_mu, q_out, v_out or params; tau_ld < 24; sweeps < 0; dt not finite and
+ * > 0; erp outside [0, 1]; cfm < 0; a non-finite ground_z; a wrong struct_size.
+ * cmpc_walk_plant_default_params: struct_size, sweeps = 50, dt = 0.01, ground_z = 0, erp = 0.2, cfm = 0.  These are starting
+ * values, NOT validated ones: on a standing HRP-4 from a cold start 30 sweeps leave |v+| at 2.7e-2, 100 at 5e-4; read
+ * `residual`.
+ *
  * The launches are asynchronous on `stream` (hipStream_t; NULL = default stream), allocate nothing and do not synchronise
  * the host.  Every function returns 0 on success; message via cmpc_walk_last_error.
  */
@@ -84,6 +122,18 @@ int cmpc_walk_integrate(int device, int32_t B, const double *q, const double *v,
 
 int cmpc_walk_measure(int device, int32_t B, const double *centroid, const double *pose, double z_min, double cos_tilt_min,
                       double *state, uint8_t *alive, double *x_meas, double *innovation, void *stream);
+
+typedef struct cmpc_walk_plant_params {
+  int32_t struct_size, sweeps;     /* sizeof(cmpc_walk_plant_params); Gauss-Seidel sweeps over the eight vertices */
+  double dt, ground_z, erp, cfm;   /* time step; floor height; share of a penetration removed per tick; W's diagonal term */
+} cmpc_walk_plant_params;
+
+void cmpc_walk_plant_default_params(cmpc_walk_plant_params *p);
+
+int cmpc_walk_plant_step(int device, int32_t B, const double *q, const double *v, const double *M, const double *h,
+                         const double *J, const double *pose, const double *tau, int32_t tau_ld, const double *ext,
+                         const double *foot_mu, const uint8_t *hold, const cmpc_walk_plant_params *params,
+                         double *impulse, double *q_out, double *v_out, int32_t *status, double *residual, void *stream);
 
 const char *cmpc_walk_last_error(void);
 

@@ -29,13 +29,19 @@ RBD_SYMBOLS = ("cmpc_rbd_model_create", "cmpc_rbd_model_destroy", "cmpc_rbd_eval
 
 #: every symbol include/cmpc_walk.h declares (task references and state integrator of the walking loop, same library)
 WALK_SYMBOLS = ("cmpc_walk_gait_create", "cmpc_walk_gait_destroy", "cmpc_walk_task_refs", "cmpc_walk_integrate",
-                "cmpc_walk_measure", "cmpc_walk_last_error")
+                "cmpc_walk_measure", "cmpc_walk_plant_step", "cmpc_walk_plant_default_params", "cmpc_walk_last_error")
 
 
 class WbcGains(ctypes.Structure):
     """``cmpc_wbc_gains`` of include/cmpc_wbc.h; task order lfoot, rfoot, com, torso, base, joints."""
     _fields_ = [("struct_size", ctypes.c_int32), ("reserved", ctypes.c_int32), ("weight", ctypes.c_double * 6),
                 ("pos_gain", ctypes.c_double * 6), ("vel_gain", ctypes.c_double * 6)]
+
+
+class PlantParams(ctypes.Structure):
+    """``cmpc_walk_plant_params`` of include/cmpc_walk.h."""
+    _fields_ = [("struct_size", ctypes.c_int32), ("sweeps", ctypes.c_int32), ("dt", ctypes.c_double), ("ground_z", ctypes.c_double),
+                ("erp", ctypes.c_double), ("cfm", ctypes.c_double)]
 
 
 _lib = None
@@ -125,6 +131,10 @@ def load():
     lib.cmpc_walk_integrate.restype = ctypes.c_int
     lib.cmpc_walk_measure.argtypes = [ctypes.c_int, i32, vp, vp, f64, f64, vp, vp, vp, vp, vp]
     lib.cmpc_walk_measure.restype = ctypes.c_int
+    lib.cmpc_walk_plant_step.argtypes = [ctypes.c_int, i32] + [vp] * 7 + [i32, vp, vp, vp, ctypes.POINTER(PlantParams)] + [vp] * 6
+    lib.cmpc_walk_plant_step.restype = ctypes.c_int
+    lib.cmpc_walk_plant_default_params.argtypes = [ctypes.POINTER(PlantParams)]
+    lib.cmpc_walk_plant_default_params.restype = None
     lib.cmpc_walk_last_error.argtypes = []
     lib.cmpc_walk_last_error.restype = ctypes.c_char_p
     lib.cmpc_version.argtypes = []

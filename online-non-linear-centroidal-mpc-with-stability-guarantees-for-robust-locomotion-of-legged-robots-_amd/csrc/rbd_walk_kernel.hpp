@@ -239,6 +239,24 @@ CMPC_DEV void refs_instance(const Gait &G, size_t b, const int32_t *t_all, const
   CMPC_SYNC();
 }
 
+// q+ (QO) from q (Q) and the new velocity (VO), all LDS: lane 0 the base, lanes 6..29 the joints (include/cmpc_walk.h).
+CMPC_DEV void integrate_pose(const double *Q, const double *VO, double dt, double *QO, int lane) {
+  if (lane == 0) {
+    const double w[3] = {Q[0], Q[1], Q[2]};
+    const double dw[3] = {dt * VO[0], dt * VO[1], dt * VO[2]}, vb[3] = {VO[3], VO[4], VO[5]};
+    double R[9], dR[9], Rn[9], wn[3], vw[3];
+    cmpc_rbd::exp_so3(w, R);
+    cmpc_rbd::exp_so3(dw, dR);
+    cmpc_rbd::matmul3(R, dR, Rn);
+    cmpc_rbd::log_so3(Rn, wn);
+    cmpc_rbd::matvec3(R, vb, vw);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { QO[k] = wn[k]; QO[3 + k] = Q[3 + k] + dt * vw[k]; }
+  } else if (lane >= 6 && lane < ND) {
+    QO[lane] = Q[lane] + dt * VO[lane];
+  }
+}
+
 // One robot's explicit step in the body-twist convention of include/cmpc_rbd.h; in place is allowed (every word is in LDS
 // before the first store).  lds: INTEGRATE_LDS_DOUBLES.
 CMPC_DEV void integrate_instance(size_t b, const double *q, const double *v, const double *qdd, double dt, const uint8_t *hold,
@@ -262,20 +280,7 @@ CMPC_DEV void integrate_instance(size_t b, const double *q, const double *v, con
   }
   if (lane < ND) VO[lane] = V[lane] + dt * A[lane];
   CMPC_SYNC();
-  if (lane == 0) {
-    const double w[3] = {Q[0], Q[1], Q[2]};
-    const double dw[3] = {dt * VO[0], dt * VO[1], dt * VO[2]}, vb[3] = {VO[3], VO[4], VO[5]};
-    double R[9], dR[9], Rn[9], wn[3], vw[3];
-    cmpc_rbd::exp_so3(w, R);
-    cmpc_rbd::exp_so3(dw, dR);
-    cmpc_rbd::matmul3(R, dR, Rn);
-    cmpc_rbd::log_so3(Rn, wn);
-    cmpc_rbd::matvec3(R, vb, vw);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { QO[k] = wn[k]; QO[3 + k] = Q[3 + k] + dt * vw[k]; }
-  } else if (lane >= 6 && lane < ND) {
-    QO[lane] = Q[lane] + dt * VO[lane];
-  }
+  integrate_pose(Q, VO, dt, QO, lane);
   CMPC_SYNC();
   if (lane < ND) { q_out[b * ND + lane] = QO[lane]; v_out[b * ND + lane] = VO[lane]; }
   CMPC_SYNC();

@@ -9,6 +9,9 @@ fallback.  ``Gait``, ``BatchedRobot.task_references``, ``integrate`` and ``walki
 (include/cmpc_walk.h, csrc/rbd_walk_kernel.hpp): the task references of a walking robot from its own adapted plan, and the
 step from the QP's acceleration to the next tick's (q, v).  ``BatchedRobot.measure`` (``cmpc_walk_measure``,
 csrc/walk_measure_kernel.hpp) feeds the robot's own centroid and foot angles back into the state its MPC starts from.
+``Plant`` and ``BatchedRobot.simulate`` (``cmpc_walk_plant_step``, csrc/walk_plant_kernel.hpp) are the contact plant: the QP's
+torques, a wrench on the base and a flat frictional floor under the sole vertices move the robot instead of the QP's
+acceleration.
 
 Coordinates (this build's own: parity with DART's is not pinned by any test): q[0:3] is the rotation
 vector of the base, R_b = Exp(q[0:3]) (world <- base), q[3:6] the base origin in the world, q[6+k] the joint angles in URDF
@@ -42,6 +45,40 @@ References = collections.namedtuple("References", "ff pos_err vel_err feet_des")
 REFERENCE_FIELDS = References._fields
 #: the optional outputs of ``cmpc_walk_measure``: the measured x0 (B,20) and measured minus predicted (B,9)
 Measurement = collections.namedtuple("Measurement", "x_meas innovation")
+#: what ``cmpc_walk_plant_step`` returns: the next (q, v) (B,30), the contact impulses (B,24), status (B,) int32 (0 stepped,
+#: 1 held, 2 refused) and the normal velocity in m/s by which the step still violates non-penetration (B,)
+PlantStep = collections.namedtuple("PlantStep", "q v impulse status residual")
+PLANT_OUTPUTS = ("impulse", "status", "residual")
+IMPULSE_WORDS = 24
+
+
+class Plant:
+    """The parameters of the contact plant (``cmpc_walk_plant_params`` of include/cmpc_walk.h): the time step ``dt``, the
+    number of Gauss-Seidel ``sweeps`` over the eight sole vertices, the share ``erp`` of a penetration that a tick removes,
+    the diagonal term ``cfm`` of the contact matrix and the height ``ground_z`` of the floor.  The defaults are starting
+    values, not validated ones: ``PlantStep.residual`` says whether the sweeps were enough.  Needs no device."""
+
+    def __init__(self, dt, sweeps=50, erp=0.2, cfm=0.0, ground_z=0.0):
+        if isinstance(sweeps, bool) or int(sweeps) != sweeps or sweeps < 0:
+            raise ValueError("sweeps must be an integer >= 0")
+        dt, erp, cfm, ground_z = float(dt), float(erp), float(cfm), float(ground_z)
+        if not (np.isfinite(dt) and dt > 0.):
+            raise ValueError("dt must be finite and > 0")
+        if not 0. <= erp <= 1.:
+            raise ValueError("erp must be in [0, 1]")
+        if not (np.isfinite(cfm) and cfm >= 0.):
+            raise ValueError("cfm must be finite and >= 0")
+        if not np.isfinite(ground_z):
+            raise ValueError("ground_z must be finite")
+        self.dt, self.sweeps, self.erp, self.cfm, self.ground_z = dt, int(sweeps), erp, cfm, ground_z
+
+    def params(self):
+        """The ``capi.PlantParams`` of a launch."""
+        from . import capi
+        return capi.PlantParams(ctypes.sizeof(capi.PlantParams), self.sweeps, self.dt, self.ground_z, self.erp, self.cfm)
+
+    def __repr__(self):
+        return f"Plant(dt={self.dt}, sweeps={self.sweeps}, erp={self.erp}, cfm={self.cfm}, ground_z={self.ground_z})"
 
 
 def rpy_matrix(rpy):
@@ -442,7 +479,66 @@ class BatchedRobot:
             raise RuntimeError(self._lib.cmpc_walk_last_error().decode())
         return Measurement(**out)
 
-    def walking_model(self, q, v, gait, q_ref=None, integrate=True, redundant_dofs=HRP4_REDUNDANT_DOFS, fall=None):
+    def simulate(self, q, v, ev, tau, foot_mu, plant, ext=None, hold=None, impulse=None, out=None, outputs=PLANT_OUTPUTS):
+        """One launch of ``cmpc_walk_plant_step``: (q, v) (B,30) advanced by ``plant.dt`` under the joint torques ``tau``
+        ((B,24), or a (B,24) view with unit stride along its rows such as ``solve_tasks``' tau; None: zero torques), the
+        world-frame wrench ``ext`` (B,6) = [moment, force] on the base origin (None: none) and a flat floor with friction
+        under the eight sole vertices.  ev: the ``Evaluation`` at that same (q, v) with M, h, J and pose; foot_mu (B,2):
+        half foot size and the floor's friction; plant: a ``Plant``.  hold (B,) uint8 / bool: rows that keep (q, v).
+        impulse (B,24): last tick's impulses as the warm start, overwritten with this tick's (None: a cold start; the
+        impulses are returned in a fresh tensor if ``outputs`` names them).  out: (q_out, v_out), which may be (q, v)
+        themselves; None allocates.  Returns ``PlantStep(q, v, impulse, status, residual)`` on the current stream; status
+        and residual are None unless in ``outputs``."""
+        import torch
+        if not isinstance(plant, Plant):
+            raise ValueError("plant must be a rbd.Plant")
+        B = q.shape[0]
+        self._checked("q", q, (B, DOFS))
+        self._checked("v", v, (B, DOFS))
+        self._checked("ev.M", ev.M, (B, DOFS, DOFS))
+        self._checked("ev.h", ev.h, (B, DOFS))
+        self._checked("ev.J", ev.J, (B, ROWS, DOFS))
+        self._checked("ev.pose", ev.pose, (B, ROWS))
+        tau_ld = DOFS - BASE
+        if tau is not None:
+            if not (torch.is_tensor(tau) and tau.is_cuda and tau.dtype == torch.float64 and tuple(tau.shape) == (B, DOFS - BASE)
+                    and tau.device == self.device and (B == 0 or tau.stride(1) == 1) and (B <= 1 or tau.stride(0) >= DOFS - BASE)):
+                raise ValueError(f"tau must be a fp64 tensor of shape ({B}, {DOFS - BASE}) on {self.device} with unit stride "
+                                 f"along its rows and a row stride >= {DOFS - BASE}")
+            tau_ld = tau.stride(0) if B > 1 else DOFS - BASE
+        self._checked("foot_mu", foot_mu, (B, 2))
+        if ext is not None:
+            self._checked("ext", ext, (B, 6))
+        if hold is not None:
+            if torch.is_tensor(hold) and hold.dtype == torch.bool:
+                hold = hold.view(torch.uint8)                     # (same bytes: True is 1)
+            self._checked("hold", hold, (B,), torch.uint8)
+        unknown = set(outputs) - set(PLANT_OUTPUTS)
+        if unknown:
+            raise ValueError(f"unknown outputs {sorted(unknown)}")
+        if impulse is not None:
+            self._checked("impulse", impulse, (B, IMPULSE_WORDS))
+        elif "impulse" in outputs:
+            impulse = torch.zeros((B, IMPULSE_WORDS), dtype=torch.float64, device=self.device)
+        q_out, v_out = (torch.empty_like(q), torch.empty_like(v)) if out is None else out
+        self._checked("q_out", q_out, (B, DOFS))
+        self._checked("v_out", v_out, (B, DOFS))
+        status = torch.empty((B,), dtype=torch.int32, device=self.device) if "status" in outputs else None
+        residual = torch.empty((B,), dtype=torch.float64, device=self.device) if "residual" in outputs else None
+        if B > 0:
+            ptr = lambda x: None if x is None else x.data_ptr()
+            prm = plant.params()
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            rc = self._lib.cmpc_walk_plant_step(self.device.index, B, q.data_ptr(), v.data_ptr(), ev.M.data_ptr(), ev.h.data_ptr(),
+                                                ev.J.data_ptr(), ev.pose.data_ptr(), ptr(tau), tau_ld, ptr(ext), foot_mu.data_ptr(),
+                                                ptr(hold), ctypes.byref(prm), ptr(impulse), q_out.data_ptr(), v_out.data_ptr(),
+                                                ptr(status), ptr(residual), ctypes.c_void_p(stream))
+            if rc != 0:
+                raise RuntimeError(self._lib.cmpc_walk_last_error().decode())
+        return PlantStep(q_out, v_out, impulse, status, residual)
+
+    def walking_model(self, q, v, gait, q_ref=None, integrate=True, redundant_dofs=HRP4_REDUNDANT_DOFS, fall=None, plant=None,
+                      foot_mu=None, ext=None):
         """A callable for ``BatchedRollout.attach_whole_body_tasks(qp, model)`` that walks: per tick it evaluates the
         kernel at (q, v), forms every task reference from the robot's own adapted plan (``task_references`` on the
         rollout's ``t``, ``scene_id`` and ``plan_pos``, the CoM rows from the MPC's ``desired``) and returns the
@@ -453,11 +549,27 @@ class BatchedRobot:
         Its ``measure(rollout)``, with which a rollout built with ``feedback=True`` begins its tick, evaluates (q, v) and
         launches ``measure`` on the rollout's ``state`` and ``alive`` (fall = (z_min, tilt_max): the guards of ``measure``);
         the result is kept as ``last_measurement``, and the same tick's ``model(rollout, desired)`` uses that evaluation
-        instead of launching a second one."""
+        instead of launching a second one.
+        With ``plant`` (a ``Plant``) ``advance`` launches ``simulate`` instead of ``integrate``: the tick's evaluation, the
+        QP's torques, the wrench ``ext`` ((B,6), which the caller may rewrite between ticks: that is how a fleet is pushed)
+        and the floor move the robot, with hold = not alive.  A robot whose QP failed is not held: it receives the zeros
+        the QP returned and goes limp under gravity.  foot_mu (B,2): half foot size and the floor's friction (None: 0.05
+        and the rollout's ``state[:, 15]`` at the first tick).  ``impulse`` (B,24) carries the warm start from tick to tick
+        and ``last_plant`` keeps the tick's ``PlantStep``."""
         import torch
         sel = torch.from_numpy(self.model.joint_selection(redundant_dofs)).to(self.device)
         q_ref = q[0].clone() if q_ref is None else q_ref
         z_min, tilt_max = (-np.inf, None) if fall is None else fall
+        if plant is not None and not isinstance(plant, Plant):
+            raise ValueError("plant must be a rbd.Plant or None")
+        if plant is None and (foot_mu is not None or ext is not None):
+            raise ValueError("foot_mu and ext go with a plant")
+        B = q.shape[0]
+        if foot_mu is not None:
+            self._checked("foot_mu", foot_mu, (B, 2))
+        if ext is not None:
+            self._checked("ext", ext, (B, 6))
+        floor = [foot_mu]
         measured = []                                             # the evaluation of a tick that began with measure()
 
         def measure(rollout):
@@ -477,10 +589,21 @@ class BatchedRobot:
             hold = (last_wbc[3] != 0) | ~rollout.alive
             self.integrate(q, v, last_wbc[1], rollout.spec.delta, hold=hold, out=(q, v))
 
+        def simulate(rollout, last_wbc):
+            if floor[0] is None:
+                floor[0] = torch.stack([torch.full_like(rollout.state[:, 15], 0.05), rollout.state[:, 15]], dim=1).contiguous()
+            ev = model.last_evaluation                           # the tick's own: (q, v) have not moved since
+            model.last_plant = self.simulate(q, v, ev, last_wbc[0], floor[0], plant, ext=ext, hold=~rollout.alive,
+                                             impulse=model.impulse, out=(q, v))
+
         model.last_evaluation = model.last_references = model.last_measurement = None
         model.measure = measure
+        if plant is not None:
+            model.impulse = torch.zeros((B, IMPULSE_WORDS), dtype=torch.float64, device=self.device)
+            model.last_plant = None
+            model.ext = ext
         if integrate:
-            model.advance = advance
+            model.advance = advance if plant is None else simulate
         return model
 
 
