@@ -22,6 +22,7 @@ KERNEL_DEPS = [os.path.join(CSRC, "cmpc_kernel.hpp"), os.path.join(CSRC, "cmpc_l
 # the solver, the batched whole-body QP (include/cmpc_wbc.h) and the batched rigid-body model (include/cmpc_rbd.h), same library
 # the device source of the batched rigid-body model (include/cmpc_rbd.h), which tests/emu/rbd_emu.cpp compiles as well
 RBD_DEPS = [os.path.join(CSRC, "rbd_kernel.hpp"), os.path.join(ROOT, "include", "cmpc_rbd.h")]
+# (rbd_inertial.hip, cmpc_rbd_eval_inertial, is that source's per-instance path: tests/emu/rbd_inertial_emu.cpp compiles it too)
 # the device source of the walking loop around it (include/cmpc_walk.h), which tests/emu/rbd_walk_emu.cpp compiles as well
 WALK_DEPS = [os.path.join(CSRC, "rbd_walk_kernel.hpp"), os.path.join(ROOT, "include", "cmpc_walk.h")]
 # the device source of the measurement that closes that loop (cmpc_walk_measure), which tests/emu/walk_measure_emu.cpp compiles as well
@@ -30,9 +31,10 @@ MEASURE_DEPS = [os.path.join(CSRC, "walk_measure_kernel.hpp"), os.path.join(ROOT
 PLANT_DEPS = [os.path.join(CSRC, "walk_plant_kernel.hpp"), os.path.join(CSRC, "rbd_walk_kernel.hpp"),
               os.path.join(ROOT, "include", "cmpc_walk.h")]
 DEVICE_UNITS = [os.path.join(CSRC, "cmpc_hip.hip"), os.path.join(CSRC, "wbc_qp.hip"), os.path.join(CSRC, "rbd.hip"),
-                os.path.join(CSRC, "rbd_walk.hip"), os.path.join(CSRC, "walk_measure.hip"), os.path.join(CSRC, "walk_plant.hip")]
+                os.path.join(CSRC, "rbd_walk.hip"), os.path.join(CSRC, "walk_measure.hip"), os.path.join(CSRC, "walk_plant.hip"),
+                os.path.join(CSRC, "rbd_inertial.hip")]
 DEVICE_DEPS = DEVICE_UNITS + KERNEL_DEPS + RBD_DEPS + WALK_DEPS + MEASURE_DEPS + PLANT_DEPS + [
-    os.path.join(CSRC, "cmpc_order_fit.h"), os.path.join(ROOT, "include", "cmpc_wbc.h")]
+    os.path.join(CSRC, "cmpc_order_fit.h"), os.path.join(CSRC, "rbd_model.h"), os.path.join(ROOT, "include", "cmpc_wbc.h")]
 EMU_DIR = os.path.join(ROOT, "tests", "emu")
 
 
@@ -139,6 +141,16 @@ def build_emu_rbd(force=False):
     return out
 
 
+def build_emu_rbd_inertial(force=False):
+    """Host emulation of the rigid-body model with per-robot inertial parameters (tests/emu/rbd_inertial_emu.cpp, on the
+    harness of rbd_emu.cpp): test harness only."""
+    src, out = os.path.join(EMU_DIR, "rbd_inertial_emu.cpp"), os.path.join(EMU_DIR, "librbd_inertial_emu.so")
+    if force or _newer(out, [src, os.path.join(EMU_DIR, "rbd_emu.cpp")] + RBD_DEPS):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-fPIC", "-shared", "-pthread",
+                               "-o", out, src])
+    return out
+
+
 def build_emu_rbd_walk(force=False):
     """Host emulation of the walking loop (tests/emu/rbd_walk_emu.cpp, with the rigid-body model's in it): test harness only."""
     src, out = os.path.join(EMU_DIR, "rbd_walk_emu.cpp"), os.path.join(EMU_DIR, "librbd_walk_emu.so")
@@ -205,6 +217,7 @@ if __name__ == "__main__":
     print(build_emu_step(force))
     print(build_emu_step(force, fused=False))
     print(build_emu_rbd(force))
+    print(build_emu_rbd_inertial(force))
     print(build_emu_rbd_walk(force))
     print(build_emu_walk_measure(force))
     print(build_emu_walk_plant(force))

@@ -33,6 +33,15 @@
  * A row of q or v with a non-finite word makes that instance's outputs NaN and touches no other instance.
  * Asynchronous on `stream` (hipStream_t; NULL = default stream); allocates nothing; no host synchronisation.
  * Returns 0 on success; message via cmpc_rbd_last_error.
+ *
+ * cmpc_rbd_eval_inertial: the same contract for a fleet whose robots carry their own inertial parameters (a payload, a
+ * domain-randomised batch).  Kinematics, frames and topology are the model's; mass, centre of mass and inertia of body i of
+ * robot b are the CMPC_RBD_INERTIAL_WORDS words of
+ *   inertial [B][25][10]  DEVICE pointer: mass, com x y z, inertia xx xy xz yy yz zz -- the host tables' words, same meaning
+ * and the total mass of robot b is its row's masses summed in body order 0 .. 24.  The table is read at every launch, so a
+ * caller may rewrite rows between launches (a robot picks a box up or drops it).  A row with a non-finite word, a mass < 0
+ * or a total that is not finite and > 0 makes that instance's outputs NaN, as a non-finite q does, and touches no other
+ * instance; that an inertia is positive definite is not checked, as on the host.  A null `inertial` is refused.
  */
 #ifndef CMPC_RBD_H
 #define CMPC_RBD_H
@@ -47,6 +56,7 @@ extern "C" {
 #define CMPC_RBD_DOFS 30   /* CMPC_WBC_DOFS */
 #define CMPC_RBD_FRAMES 4
 #define CMPC_RBD_ROWS 21   /* CMPC_WBC_TASK_ROWS */
+#define CMPC_RBD_INERTIAL_WORDS 10
 
 typedef struct cmpc_rbd_model cmpc_rbd_model;
 
@@ -57,6 +67,9 @@ int cmpc_rbd_model_destroy(cmpc_rbd_model *model);
 
 int cmpc_rbd_eval(const cmpc_rbd_model *model, int32_t B, const double *q, const double *v, double g, double *J, double *jdqd,
                   double *M, double *h, double *pose, double *vel, double *centroid, void *stream);
+int cmpc_rbd_eval_inertial(const cmpc_rbd_model *model, int32_t B, const double *q, const double *v, const double *inertial,
+                           double g, double *J, double *jdqd, double *M, double *h, double *pose, double *vel, double *centroid,
+                           void *stream);
 
 const char *cmpc_rbd_last_error(void);
 

@@ -25,7 +25,7 @@ SYMBOLS = ("cmpc_default_spec", "cmpc_create", "cmpc_destroy", "cmpc_workspace_b
 #: every symbol include/cmpc_wbc.h declares (batched whole-body QP, same library)
 WBC_SYMBOLS = ("cmpc_wbc_qp_solve_batch", "cmpc_wbc_qp_solve_tasks", "cmpc_wbc_default_gains", "cmpc_wbc_last_error")
 #: every symbol include/cmpc_rbd.h declares (batched rigid-body model, same library)
-RBD_SYMBOLS = ("cmpc_rbd_model_create", "cmpc_rbd_model_destroy", "cmpc_rbd_eval", "cmpc_rbd_last_error")
+RBD_SYMBOLS = ("cmpc_rbd_model_create", "cmpc_rbd_model_destroy", "cmpc_rbd_eval", "cmpc_rbd_eval_inertial", "cmpc_rbd_last_error")
 
 #: every symbol include/cmpc_walk.h declares (task references and state integrator of the walking loop, same library)
 WALK_SYMBOLS = ("cmpc_walk_gait_create", "cmpc_walk_gait_destroy", "cmpc_walk_task_refs", "cmpc_walk_integrate",
@@ -119,6 +119,8 @@ def load():
     lib.cmpc_rbd_model_destroy.restype = ctypes.c_int
     lib.cmpc_rbd_eval.argtypes = [vp, i32, vp, vp, f64] + [vp] * 8
     lib.cmpc_rbd_eval.restype = ctypes.c_int
+    lib.cmpc_rbd_eval_inertial.argtypes = [vp, i32, vp, vp, vp, f64] + [vp] * 8
+    lib.cmpc_rbd_eval_inertial.restype = ctypes.c_int
     lib.cmpc_rbd_last_error.argtypes = []
     lib.cmpc_rbd_last_error.restype = ctypes.c_char_p
     lib.cmpc_walk_gait_create.argtypes = [ctypes.c_int, i32, i32, i32] + [vp] * 8 + [f64, f64, ctypes.POINTER(vp)]

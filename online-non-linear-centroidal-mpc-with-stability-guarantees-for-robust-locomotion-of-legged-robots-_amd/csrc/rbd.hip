@@ -6,12 +6,7 @@
 #define CMPC_NO_DEVICE_CODE 1      // the macro layer of the solver's device source, without the solver
 #include "cmpc_kernel.hpp"
 #include "rbd_kernel.hpp"
-
-struct cmpc_rbd_model {
-  int device;
-  cmpc_rbd::Tables *tables;       // device copy of the validated tables
-  int grid_cap;                   // workgroups that are resident at once
-};
+#include "rbd_model.h"
 
 namespace {
 
@@ -30,16 +25,7 @@ __global__ void __launch_bounds__(64) rbd_eval_kernel(int B, const cmpc_rbd::Tab
 
 thread_local std::string g_rbd_err;
 
-// the caller's device is put back on every way out
-struct DeviceGuard {
-  int prev = -1, device;
-  bool ok = true;
-  explicit DeviceGuard(int d) : device(d) {
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (prev != device && hipSetDevice(device) != hipSuccess) ok = false;
-  }
-  ~DeviceGuard() { if (prev >= 0 && prev != device) (void)hipSetDevice(prev); }
-};
+using cmpc_rbd::DeviceGuard;                                      // (rbd_model.h)
 
 }  // namespace
 
@@ -100,5 +86,8 @@ int cmpc_rbd_eval(const cmpc_rbd_model *m, int32_t B, const double *q, const dou
 }
 
 const char *cmpc_rbd_last_error(void) { return g_rbd_err.c_str(); }
+
+// for the library's other translation units on this model (rbd_inertial.hip); not part of include/cmpc_rbd.h
+void cmpc_rbd_set_error(const char *msg) { g_rbd_err = msg ? msg : ""; }
 
 }  // extern "C"

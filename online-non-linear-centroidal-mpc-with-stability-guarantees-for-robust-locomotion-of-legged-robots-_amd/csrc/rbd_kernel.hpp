@@ -13,6 +13,10 @@
 //      bias accelerations, and the centroidal state
 //   6. M and J leave LDS with unit stride
 // The model's tables (cmpc_rbd::Tables) are read from global memory: they are the same for every robot of the launch.
+// run_instance<true> (csrc/rbd_inertial.hip, cmpc_rbd_eval_inertial) is the same routine for a fleet whose robots carry their
+// own inertial parameters: mass, centre of mass and inertia of every body come from the robot's own row of a device table
+// inertial[B][25][10], copied with unit stride into LDS words of its own behind J; kinematics, frames and topology stay in the
+// shared Tables.  run_instance<false> is the code it was: the switch is resolved at compile time.
 //
 // Written on the macro layer of cmpc_kernel.hpp (CMPC_DEV, CMPC_LANE, CMPC_SYNC, CMPC_FMA): hipcc compiles it for the product
 // library (csrc/rbd.hip), g++ for the CPU test harness (tests/emu/rbd_emu.cpp), where the lanes are threads and CMPC_SYNC is
@@ -51,7 +55,9 @@ struct Tables {
 enum {
   L_Q = 0, L_V = 32, L_R = 64, L_P = L_R + 9 * NB, L_S = L_P + 3 * NB, L_VEL = L_S + 6 * ND,
   L_ACC = L_VEL + 6 * NB, L_I = L_ACC + 6 * NB, L_MOM = L_I + 10 * NB, L_F = L_MOM + 6 * NB, L_M = L_F + 6 * NB,
-  L_J = L_M + ND * ND, LDS_DOUBLES = L_J + ROWS * ND
+  L_J = L_M + ND * ND, LDS_DOUBLES = L_J + ROWS * ND,
+  // the per-instance kernel: the robot's own row behind J, which nothing else writes (phase 3's zeroing ends at J's end)
+  IW = CMPC_RBD_INERTIAL_WORDS, L_IR = LDS_DOUBLES, LDS_DOUBLES_INERTIAL = L_IR + IW * NB
 };
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -257,16 +263,36 @@ CMPC_DEV void log_so3(const double *R, double *w) {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // One robot.  q, v and the outputs point at the instance's own rows (outputs may be null); lds: LDS_DOUBLES doubles.
+// INERTIAL: irow is the robot's own [25][10] row (mass, com xyz, inertia xx xy xz yy yz zz per body) and lds has
+// LDS_DOUBLES_INERTIAL doubles; T's mass, com, inertia and total_mass are not read.
+template <bool INERTIAL = false>
 CMPC_DEV void run_instance(const Tables *T, const double *q, const double *v, double g, double *J, double *jdqd, double *M,
-                           double *h, double *pose, double *vel, double *centroid, double *lds) {
+                           double *h, double *pose, double *vel, double *centroid, double *lds, const double *irow = nullptr) {
   const int lane = CMPC_LANE;
   double *Q = lds + L_Q, *Vq = lds + L_V, *Rw = lds + L_R, *Pw = lds + L_P, *S = lds + L_S, *VEL = lds + L_VEL;
   double *ACC = lds + L_ACC, *IN = lds + L_I, *MOM = lds + L_MOM, *FRC = lds + L_F, *Ml = lds + L_M, *Jl = lds + L_J;
 
   // 0. the instance's row; a non-finite word anywhere in it -- or a base rotation vector whose squared norm is not finite --
   // makes every output NaN.  Every lane writes a flag word of its own (in M's window, idle until phase 3) and all of them
-  // read the thirty: no word has two writers.
-  if (lane < ND) {
+  // read the thirty (INERTIAL: the sixty-four): no word has two writers.
+  double *IR = lds + L_IR;                                        // (INERTIAL only: the end of lds otherwise)
+  double mtot_own = 0.0;
+  if constexpr (INERTIAL) {
+    // the robot's own row as well, with unit stride: lane l copies words l, l + 64, ... and judges the words it copied (a
+    // non-finite word, or a mass < 0: word 0 of a body's ten), so here every one of the 64 lanes writes a flag word
+    double flag = 0.0;
+    if (lane < ND) {
+      const double qi = q[lane], vi = v[lane];
+      Q[lane] = qi; Vq[lane] = vi;
+      if (!(dev_finite(qi) && dev_finite(vi))) flag = 1.0;
+    }
+    for (int i = lane; i < IW * NB; i += 64) {
+      const double w = irow[i];
+      IR[i] = w;
+      if (!dev_finite(w) || (i % IW == 0 && !(w >= 0.0))) flag = 1.0;
+    }
+    Ml[lane] = flag;
+  } else if (lane < ND) {
     const double qi = q[lane], vi = v[lane];
     Q[lane] = qi; Vq[lane] = vi;
     Ml[lane] = (dev_finite(qi) && dev_finite(vi)) ? 0.0 : 1.0;
@@ -274,6 +300,12 @@ CMPC_DEV void run_instance(const Tables *T, const double *q, const double *v, do
   CMPC_SYNC();
   bool bad = !dev_finite(Q[0] * Q[0] + Q[1] * Q[1] + Q[2] * Q[2]);
   for (int k = 0; k < ND; ++k) bad = bad || Ml[k] != 0.0;
+  if constexpr (INERTIAL) {
+    for (int k = ND; k < 64; ++k) bad = bad || Ml[k] != 0.0;
+    // the total in fill_tables' order, bodies 0 .. 24, by every lane for itself: the same bits in all of them
+    for (int i = 0; i < NB; ++i) mtot_own += IR[IW * i];
+    bad = bad || !dev_finite(mtot_own) || !(mtot_own > 0.0);
+  }
   if (bad) {
     const double nan = __builtin_nan("");
     if (J) for (int i = lane; i < ROWS * ND; i += 64) J[i] = nan;
@@ -370,10 +402,11 @@ CMPC_DEV void run_instance(const Tables *T, const double *q, const double *v, do
     double R[9], c[3], t[9], Ic[9];
 #pragma unroll
     for (int k = 0; k < 9; ++k) R[k] = Rw[9 * lane + k];
-    matvec3(R, T->com[lane], c);
+    const double *ir = INERTIAL ? IR + IW * lane : nullptr;      // the body's own ten words
+    matvec3(R, INERTIAL ? ir + 1 : T->com[lane], c);
 #pragma unroll
     for (int k = 0; k < 3; ++k) c[k] = Pw[3 * lane + k] + c[k];
-    const double *ib = T->inertia[lane];
+    const double *ib = INERTIAL ? ir + 4 : T->inertia[lane];
     const double Ib[9] = {ib[0], ib[1], ib[2], ib[1], ib[3], ib[4], ib[2], ib[4], ib[5]};
     matmul3(R, Ib, t);
     // Ic = t R' (its upper triangle is used)
@@ -381,7 +414,7 @@ CMPC_DEV void run_instance(const Tables *T, const double *q, const double *v, do
     for (int i = 0; i < 3; ++i)
 #pragma unroll
       for (int j = 0; j < 3; ++j) Ic[3 * i + j] = t[3 * i] * R[3 * j] + t[3 * i + 1] * R[3 * j + 1] + t[3 * i + 2] * R[3 * j + 2];
-    const double m = T->mass[lane], cc = dot3(c, c);
+    const double m = INERTIAL ? ir[0] : T->mass[lane], cc = dot3(c, c);
     double I[10];
     I[0] = m; I[1] = m * c[0]; I[2] = m * c[1]; I[3] = m * c[2];
     I[4] = Ic[0] + m * (cc - c[0] * c[0]); I[5] = 0.5 * (Ic[1] + Ic[3]) - m * (c[0] * c[1]); I[6] = 0.5 * (Ic[2] + Ic[6]) - m * (c[0] * c[2]);
@@ -419,7 +452,7 @@ CMPC_DEV void run_instance(const Tables *T, const double *q, const double *v, do
   CMPC_SYNC();
 
   // 5. one lane per dof; lanes 32..35 the task frames, lane 36 the centroidal state
-  const double mtot = T->total_mass;
+  const double mtot = INERTIAL ? mtot_own : T->total_mass;
   if (lane < ND) {
     const int b = lane < 6 ? 0 : lane - 5;
     double Sj[6], Ic[10], F[6], Fb[6], W[6];

@@ -11,7 +11,9 @@ step from the QP's acceleration to the next tick's (q, v).  ``BatchedRobot.measu
 csrc/walk_measure_kernel.hpp) feeds the robot's own centroid and foot angles back into the state its MPC starts from.
 ``Plant`` and ``BatchedRobot.simulate`` (``cmpc_walk_plant_step``, csrc/walk_plant_kernel.hpp) are the contact plant: the QP's
 torques, a wrench on the base and a flat frictional floor under the sole vertices move the robot instead of the QP's
-acceleration.
+acceleration.  ``BatchedRobot(inertial=...)`` (``cmpc_rbd_eval_inertial``, csrc/rbd_inertial.hip) gives every robot of the batch
+its own link masses, centres of mass and inertias -- ``RobotModel.inertial`` is the model's row and ``attach_payload`` welds a
+load to a body --, and everything above sees that robot, since it all goes through ``evaluate``.
 
 Coordinates (this build's own: parity with DART's is not pinned by any test): q[0:3] is the rotation
 vector of the base, R_b = Exp(q[0:3]) (world <- base), q[3:6] the base origin in the world, q[6+k] the joint angles in URDF
@@ -253,13 +255,30 @@ class RobotModel:
             if frames[name] not in place:
                 raise ValueError(f"task frame {name!r}: the URDF has no link {frames[name]!r}")
             fb[k], fR[k], fp[k] = place[frames[name]]
-        return cls(parent, joint_R, joint_p, axis, mass, com, inertia, fb, fR, fp, joint_names=[j['name'] for j in moving])
+        model = cls(parent, joint_R, joint_p, axis, mass, com, inertia, fb, fR, fp, joint_names=[j['name'] for j in moving])
+        model.link_body = {n: int(b) for n, (b, _, _) in place.items()}
+        return model
 
     # ---- host helpers ----------------------------------------------------------------------------------------------------
     def tables(self):
         """The arrays of ``cmpc_rbd_model_create``, in its argument order."""
         return (self.parent, self.joint_R, self.joint_p, self.axis, self.mass, self.com, self.inertia, self.frame_body,
                 self.frame_R, self.frame_p)
+
+    def inertial(self):
+        """The model's inertial table (25, 10): per body mass, centre of mass xyz, inertia xx xy xz yy yz zz -- one robot's
+        row of ``BatchedRobot(inertial=...)`` (a new array)."""
+        return np.concatenate([self.mass[:, None], self.com, self.inertia], axis=1)
+
+    def body_of(self, link_name):
+        """The body (0..24) that carries the URDF link ``link_name``: the link's own if a moving joint leads to it, otherwise
+        the one it was merged into.  Only a model that ``from_urdf`` parsed knows its links."""
+        links = getattr(self, "link_body", None)
+        if links is None:
+            raise ValueError("this model was not parsed from a URDF: it has no link names")
+        if link_name not in links:
+            raise ValueError(f"the URDF has no link {link_name!r}")
+        return links[link_name]
 
     def joint_selection(self, names):
         """The diagonal (30,) of ``joint_selection`` (code/inverse_dynamics.py:24-28): 1 at the dofs named."""
@@ -301,10 +320,68 @@ class RobotModel:
         return q
 
 
-class BatchedRobot:
-    """``RobotModel`` on the GPU: ``evaluate(q, v)`` is one launch of csrc/rbd_kernel.hpp for the whole batch."""
+INERTIAL_WORDS = 10
 
-    def __init__(self, model, device="cuda:0", g=9.81):
+
+def _parallel_axes(m, d):
+    """m (|d|^2 1 - d d') as xx xy xz yy yz zz: m (...,), d (...,3) -> (...,6)."""
+    dd = np.sum(d * d, axis=-1)
+    return m[..., None] * np.stack([dd - d[..., 0] * d[..., 0], -d[..., 0] * d[..., 1], -d[..., 0] * d[..., 2],
+                                    dd - d[..., 1] * d[..., 1], -d[..., 1] * d[..., 2], dd - d[..., 2] * d[..., 2]], axis=-1)
+
+
+def attach_payload(inertial, body, mass, at, inertia=None):
+    """An inertial table (..., 25, 10) (``RobotModel.inertial()``, or a batch of them) with a rigid mass welded to ``body`` at
+    the point ``at`` (3,) of the body's frame: mass, centre of mass and inertia of that body are combined by the
+    parallel-axis rule about the new centre of mass.  ``inertia``: the payload's own about its centre of mass in the body's
+    axes, (3,3) or xx xy xz yy yz zz (None: a point mass).  ``body``, ``mass`` and ``at`` (and ``inertia``) broadcast
+    against the table's leading dimensions, so ``attach_payload(model.inertial(), b, np.array([0., 0.7, 2.5]), at)`` is a
+    sweep of three robots.  Returns a new array; a robot whose payload has zero mass keeps its row's bits.  Numpy only."""
+    tab = np.asarray(inertial, dtype=np.float64)
+    if tab.ndim < 2 or tab.shape[-2:] != (BODIES, INERTIAL_WORDS):
+        raise ValueError(f"inertial must have shape (..., {BODIES}, {INERTIAL_WORDS}), got {tab.shape}")
+    body, mass, at = np.asarray(body), np.asarray(mass, dtype=np.float64), np.asarray(at, dtype=np.float64)
+    if body.dtype.kind not in "iu" or np.any(body < 0) or np.any(body >= BODIES):
+        raise ValueError(f"body must be an integer in 0..{BODIES - 1}")
+    if not (np.all(np.isfinite(mass)) and np.all(mass >= 0.)):
+        raise ValueError("the payload's mass must be finite and >= 0")
+    if at.shape[-1:] != (3,) or not np.all(np.isfinite(at)):
+        raise ValueError("at must be a finite point (..., 3) of the body's frame")
+    own = np.zeros(6)
+    if inertia is not None:
+        own = np.asarray(inertia, dtype=np.float64)
+        if own.shape[-2:] == (3, 3):
+            own = np.stack([own[..., 0, 0], own[..., 0, 1], own[..., 0, 2], own[..., 1, 1], own[..., 1, 2], own[..., 2, 2]], axis=-1)
+        if own.shape[-1:] != (6,) or not np.all(np.isfinite(own)):
+            raise ValueError("inertia must be finite, (..., 3, 3) or (..., 6) = xx xy xz yy yz zz")
+    lead = np.broadcast_shapes(tab.shape[:-2], body.shape, mass.shape, at.shape[:-1], own.shape[:-1])
+    out = np.array(np.broadcast_to(tab, lead + tab.shape[-2:]), order='C')           # (a copy: writable, C-contiguous)
+    body, mass = np.broadcast_to(body, lead), np.broadcast_to(mass, lead)
+    at, own = np.broadcast_to(at, lead + (3,)), np.broadcast_to(own, lead + (6,))
+    row = np.take_along_axis(out, body[..., None, None], axis=-2)[..., 0, :]      # (..., 10): the body's words
+    m0, c0, I0 = row[..., 0], row[..., 1:4], row[..., 4:10]
+    m = m0 + mass
+    c = (m0[..., None] * c0 + mass[..., None] * at) / np.where(m > 0., m, 1.)[..., None]
+    I = I0 + _parallel_axes(m0, c0 - c) + own + _parallel_axes(mass, at - c)
+    new = np.where((mass > 0.)[..., None], np.concatenate([m[..., None], c, I], axis=-1), row)
+    np.put_along_axis(out, body[..., None, None], new[..., None, :], axis=-2)
+    return out
+
+
+class BatchedRobot:
+    """``RobotModel`` on the GPU: ``evaluate(q, v)`` is one launch of csrc/rbd_kernel.hpp for the whole batch.
+
+    ``inertial``: a contiguous fp64 (B, 25, 10) tensor on the device gives every robot of the batch its own link masses,
+    centres of mass and inertias (``RobotModel.inertial()`` is the model's row, ``attach_payload`` welds a load to a body);
+    ``evaluate`` then launches ``cmpc_rbd_eval_inertial`` (csrc/rbd_inertial.hip), and everything that goes through it --
+    ``task_model``, ``walking_model``, ``measure``, ``simulate`` -- sees the robot it describes.  The tensor is read at every
+    launch and kept by reference: rewriting a row between ticks picks a box up or drops it.  A row with a non-finite word, a
+    negative mass or no mass at all makes that robot's evaluation NaN.  None (the default): the shared model, as before.
+
+    The MPC is told separately: ``BatchedRollout(mass=robot.total_mass)`` plans for the robot that is simulated, while the
+    rollout's default, the scene's mass, leaves the payload unknown to the MPC -- the reference's payload experiment."""
+
+    def __init__(self, model, device="cuda:0", g=9.81, inertial=None):
         import torch
         from . import capi
         if not torch.cuda.is_available():
@@ -320,22 +397,52 @@ class BatchedRobot:
         if rc != 0:
             raise ValueError(self._lib.cmpc_rbd_last_error().decode())
         self.joint_sel = None
+        self._inertial = None
+        self.set_inertial(inertial)
 
     def __del__(self):
         h, self._handle = getattr(self, "_handle", None), None
         if h:
             self._lib.cmpc_rbd_model_destroy(h)
 
+    def set_inertial(self, t):
+        """Every robot's own inertial table: a contiguous fp64 (B, 25, 10) tensor on this GPU, kept by reference and read at
+        every ``evaluate`` (B must be that call's batch), or None for the shared model's."""
+        import torch
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.dim() == 3
+                                  and tuple(t.shape[1:]) == (BODIES, INERTIAL_WORDS) and t.device == self.device):
+            raise ValueError(f"inertial must be a contiguous fp64 tensor of shape (B, {BODIES}, {INERTIAL_WORDS}) on {self.device}, "
+                             f"or None")
+        self._inertial = t
+
+    @property
+    def inertial(self):
+        """The tensor of ``set_inertial``, or None."""
+        return self._inertial
+
+    @property
+    def total_mass(self):
+        """The model's total mass (a float); with an inertial table a (B,) tensor, every robot's own as the kernel forms
+        it: its row's masses summed in body order, at the table's present contents."""
+        if self._inertial is None:
+            return self.model.total_mass
+        total = self._inertial[:, 0, 0].clone()
+        for i in range(1, BODIES):
+            total = total + self._inertial[:, i, 0]
+        return total
+
     def evaluate(self, q, v, outputs=Evaluation._fields):
         """q, v (B,30) contiguous fp64 on this GPU -> ``Evaluation(J (B,21,30), jdqd (B,21), M (B,30,30), h (B,30), pose
         (B,21), vel (B,21), centroid (B,9))`` on the current stream.  ``outputs``: the fields wanted; the others are None
-        (the kernel skips them)."""
+        (the kernel skips them).  With an inertial table (``set_inertial``) robot b is evaluated with row b of it."""
         import torch
         B = q.shape[0]
         for name, t in (("q", q), ("v", v)):
             if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous()
                     and tuple(t.shape) == (B, DOFS) and t.device == self.device):
                 raise ValueError(f"{name} must be a contiguous fp64 tensor of shape ({B}, {DOFS}) on {self.device}")
+        if self._inertial is not None and self._inertial.shape[0] != B:
+            raise ValueError(f"the inertial table holds {self._inertial.shape[0]} robots, q and v {B}")
         shapes = dict(J=(B, ROWS, DOFS), jdqd=(B, ROWS), M=(B, DOFS, DOFS), h=(B, DOFS), pose=(B, ROWS), vel=(B, ROWS),
                       centroid=(B, 9))
         unknown = set(outputs) - set(shapes)
@@ -344,9 +451,12 @@ class BatchedRobot:
         out = {k: (torch.empty(shapes[k], dtype=torch.float64, device=self.device) if k in outputs else None) for k in Evaluation._fields}
         if B > 0:
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            rc = self._lib.cmpc_rbd_eval(self._handle, B, q.data_ptr(), v.data_ptr(), self.g,
-                                         *(None if out[k] is None else out[k].data_ptr() for k in Evaluation._fields),
-                                         ctypes.c_void_p(stream))
+            ptrs = [None if out[k] is None else out[k].data_ptr() for k in Evaluation._fields]
+            if self._inertial is None:
+                rc = self._lib.cmpc_rbd_eval(self._handle, B, q.data_ptr(), v.data_ptr(), self.g, *ptrs, ctypes.c_void_p(stream))
+            else:
+                rc = self._lib.cmpc_rbd_eval_inertial(self._handle, B, q.data_ptr(), v.data_ptr(), self._inertial.data_ptr(), self.g,
+                                                      *ptrs, ctypes.c_void_p(stream))
             if rc != 0:
                 raise RuntimeError(self._lib.cmpc_rbd_last_error().decode())
         return Evaluation(**out)
